@@ -24,6 +24,12 @@ The N > 1 job is bootstrapped without torch (psg_group.SocketGroup: a loopback
 star with rank 0 as the rendezvous), so libpsgpu.so runs on /opt/rocm's HIP and
 RCCL at every N; the line names the libraries the process mapped.
 
+A plain run sets up, warms up, times --steps steps and prints the line (Push /
+Pull kernel times and their roofline fractions come from events recorded in the
+timed steps).  --full adds what takes runs of its own: the parity check, the
+256 M north-star probe and copy ceilings, the batched and accumulate probes and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step returned.
+
 Prints ONE JSON line on rank 0.  Launch for N > 1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N
@@ -83,6 +89,39 @@ STRETCH_PUSH_BYTES = 12
 # pushes outside warmup + steps that a run may make (calibration, verification)
 BATCHED = 20  # requests per batch of the cached-stretch line's batched timing
 EXTRA_PUSH_BOUND = 64
+# --dump-outputs: an output of more values than this is written as a sample of
+# this many, at positions drawn once with DUMP_SEED (16 MiB as float32)
+DUMP_MAX_VALUES = 4 << 20
+DUMP_SEED = 20240
+
+
+def dump_positions(n: int):
+    """The positions of an n-value output that --dump-outputs writes: all of
+    them (None) up to DUMP_MAX_VALUES, else a sorted sample that depends on n
+    alone, so two runs with the same arguments write the same elements."""
+    import numpy as np
+    if n <= DUMP_MAX_VALUES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_VALUES, replace=False))
+
+
+def dump_device_vector(directory: str, name: str, buf, n: int, npt, vb: int, stream) -> None:
+    """Write the n values of device buffer `buf` (or their dump_positions
+    sample) to directory/name.npy as float32, read back in pieces."""
+    import numpy as np
+    idx = dump_positions(n)
+    os.makedirs(directory, exist_ok=True)
+    if idx is None:
+        got = buf.download(npt, n, stream)
+    else:
+        got = np.empty(len(idx), npt)
+        piece = 16 << 20
+        for lo in range(0, n, piece):
+            a, b = np.searchsorted(idx, (lo, lo + piece))
+            if b > a:
+                part = buf.download(npt, min(piece, n - lo), stream, offset=lo * vb)
+                got[a:b] = part[idx[a:b] - lo]
+    np.save(os.path.join(directory, name + ".npy"), got.astype(np.float32))
 
 
 class GpuBackend:
@@ -661,6 +700,14 @@ class GpuBackend:
         self.stream.sync()
         self.p.device_sync()
 
+    def dump_outputs(self, directory: str):
+        """What the worker received from the last step: the pulled vector (every
+        shard's block at N > 1), as pull.npy (pull_rank<r>.npy on rank r > 0)."""
+        import numpy as np
+        npt = {self.p.F32: np.float32, self.p.F16: np.float16}[self.dt]
+        name = "pull" if self.rank == 0 else f"pull_rank{self.rank}"
+        dump_device_vector(directory, name, self.out, self.L, npt, self.vb, self.stream)
+
     def accumulate_probe(self, iters=10):
         """The dominant local kernel at N > 1: the shard accumulate after the
         reduce-scatter (12 B per f32 element), timed alone with HIP events.
@@ -837,6 +884,9 @@ def run(backend, args, rank: int, world: int, group=None) -> dict | None:
     L = args.keys
     assert L % world == 0, "keys must divide by the number of shards"
     group = group or _LocalGroup()
+    # a plain run: set-up, warm-up, the timed steps, the line.  --full adds the
+    # parity check, the batched / accumulate / 256 M probes and the CPU baseline
+    full = getattr(args, "full", False)
     backend._seed = args.seed
     backend.max_pushes = args.warmup + args.steps + EXTRA_PUSH_BOUND
     backend.setup(L, args.seed)
@@ -894,8 +944,12 @@ def run(backend, args, rank: int, world: int, group=None) -> dict | None:
     n_marks = max(len(sampled), 1)
     push_ms = sum(backend.elapsed(a, b) for a, b, _ in evs.values()) / n_marks
     pull_ms = sum(backend.elapsed(b, c) for _, b, c in evs.values()) / n_marks
+    if getattr(args, "dump_outputs", None) and hasattr(backend, "dump_outputs"):
+        # the last timed step's Pull, before any probe below pushes again
+        backend.dump_outputs(args.dump_outputs)
     batched = None
-    if world == 1 and getattr(backend, "cached", False) and getattr(backend, "stretch", None) is not None:
+    if (full and world == 1 and getattr(backend, "cached", False)
+            and getattr(backend, "stretch", None) is not None):
         # The LR steady state's per-request cost without a marker per request
         # (VERDICT r4 next #5): BATCHED Pushes back to back, then as many Push ->
         # Pull steps, each batch between one pair of the same timing-only events.
@@ -933,12 +987,12 @@ def run(backend, args, rank: int, world: int, group=None) -> dict | None:
         extra_pushes += 3 * BATCHED
     total_pushes = args.warmup + args.steps + extra_pushes
     chk = None
-    if args.check:
+    if full and args.check:
         # the whole pulled vector at every N, before anything else touches the shards
         chk = backend.check(total_pushes)
         if not isinstance(chk, dict):
             chk = {"ok": bool(chk)}
-    acc_ms = backend.accumulate_probe() if (world > 1 and hasattr(backend, "accumulate_probe")) else None
+    acc_ms = backend.accumulate_probe() if (full and world > 1 and hasattr(backend, "accumulate_probe")) else None
     # every rank's device, GPU and RCCL view, gathered for the line (N > 1)
     ranks = group.all_gather(backend.describe()) if (world > 1 and hasattr(backend, "describe")) else None
     ms, push_ms, pull_ms, acc = group.allreduce_max([local_ms, push_ms, pull_ms, acc_ms or 0.0])
@@ -1148,14 +1202,14 @@ def run(backend, args, rank: int, world: int, group=None) -> dict | None:
         store_mib = vb * blk / 2**20
         res["roofline"]["infinity_cache_assisted"] = store_mib <= 256
         res["roofline"]["store_mib"] = round(store_mib, 1)
-    if (world == 1 and wl == "dense" and hasattr(backend, "probe_256m")
+    if (full and world == 1 and wl == "dense" and hasattr(backend, "probe_256m")
             and not getattr(args, "no_probe256", False)):
         res["push256_roofline"] = backend.probe_256m()
         if res.get("roofline"):
             res["roofline"]["hbm_only_frac_256m"] = res["push256_roofline"]["push_frac"]
             res["roofline"]["hbm_only_note"] = ("push256_roofline: the same Push kernel on a 1 GiB store "
                                                 "(256 M floats), past the Infinity Cache")
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args)
     res["runtime_libs"] = mapped_runtime_libs()
     res["event_markers"] = ("timing-only (hipEventDisableSystemFence)" if TIMING_EVENTS
@@ -1185,9 +1239,11 @@ def run_lr(args) -> dict:
         g.fill_synth(n, p.F32, args.seed + 100 + j, 1, -1.0, 1.0, st)
     adam = p.Adam(n, lr)
     st.sync()
+    full = args.full
     sample = 4096
-    w0 = init.download(np.float32, sample)
-    g0 = [g.download(np.float32, sample) for g in grads]
+    if full:
+        w0 = init.download(np.float32, sample)
+        g0 = [g.download(np.float32, sample) for g in grads]
     init.free()
     it = 0
     for _ in range(args.warmup):
@@ -1205,34 +1261,40 @@ def run_lr(args) -> dict:
     ms = (time.perf_counter() - t0) * 1e3 / args.steps
     kernel_ms = sum(ev[i].elapsed_ms(ev[i + 1]) for i in range(args.steps)) / args.steps
     per = 4 * frames + 8 + 32
-    buf = p.DeviceBuffer(n * 4)
-    w.handle(p.PULL, None, None, buf, n, stream=st)
-    st.sync()
-    got = buf.download(np.float32, sample)
-    buf.free()
-    # the checker: the oracle's restatement of the same rounds on the sample
-    import oracle
-    ref = w0.copy()
-    m, v = np.zeros(sample), np.zeros(sample)
-    for r in range(it):
-        merged = np.zeros(sample, np.float32)
-        for g in g0:
-            merged = (merged + g).astype(np.float32)
-        oracle.lr_apply(ref, merged, 0.01, m, v, lr, 0.9, 0.999, 1e-8, r)
-    bad = int(np.count_nonzero(got.view(np.uint32) != ref.view(np.uint32)))
-    # The copy ceiling of this byte mix: the same kernel's
-    # loads and stores with a copy's arithmetic (psg_lr_mix_copy), timed the
-    # same way in this process, after the parity sample was read (it
-    # scribbles on the weights and moments).
-    cev = [p.Event(timing=TIMING_EVENTS) for _ in range(args.steps + 1)]
-    for _ in range(2):
-        p.lr_mix_copy(w, grads, n, adam, stream=st)
-    cev[0].record(st)
-    for i in range(args.steps):
-        p.lr_mix_copy(w, grads, n, adam, stream=st)
-        cev[i + 1].record(st)
-    st.sync()
-    copy_ms = sum(cev[i].elapsed_ms(cev[i + 1]) for i in range(args.steps)) / args.steps
+    bad = copy_ms = None
+    if full or args.dump_outputs:
+        buf = p.DeviceBuffer(n * 4)
+        w.handle(p.PULL, None, None, buf, n, stream=st)
+        st.sync()
+        if args.dump_outputs:
+            # the model after the last timed round, as a Pull returns it
+            dump_device_vector(args.dump_outputs, "weights", buf, n, np.float32, 4, st)
+        got = buf.download(np.float32, sample)
+        buf.free()
+    if full:
+        # the checker: the oracle's restatement of the same rounds on the sample
+        import oracle
+        ref = w0.copy()
+        m, v = np.zeros(sample), np.zeros(sample)
+        for r in range(it):
+            merged = np.zeros(sample, np.float32)
+            for g in g0:
+                merged = (merged + g).astype(np.float32)
+            oracle.lr_apply(ref, merged, 0.01, m, v, lr, 0.9, 0.999, 1e-8, r)
+        bad = int(np.count_nonzero(got.view(np.uint32) != ref.view(np.uint32)))
+        # The copy ceiling of this byte mix: the same kernel's
+        # loads and stores with a copy's arithmetic (psg_lr_mix_copy), timed the
+        # same way in this process, after the parity sample was read (it
+        # scribbles on the weights and moments).
+        cev = [p.Event(timing=TIMING_EVENTS) for _ in range(args.steps + 1)]
+        for _ in range(2):
+            p.lr_mix_copy(w, grads, n, adam, stream=st)
+        cev[0].record(st)
+        for i in range(args.steps):
+            p.lr_mix_copy(w, grads, n, adam, stream=st)
+            cev[i + 1].record(st)
+        st.sync()
+        copy_ms = sum(cev[i].elapsed_ms(cev[i + 1]) for i in range(args.steps)) / args.steps
     adam.close()
     w.close()
     for g in grads:
@@ -1246,20 +1308,22 @@ def run_lr(args) -> dict:
         "config": {"workload": f"LR BSP round: {frames} gradient frames merged + Adam over {n} features "
                                "(configs[3]'s LRServer sync apply, LRServer.h:151-178, Adam.h:28-34)",
                    "features": n, "frames": frames, "alg_bytes_per_feature": per},
-        "parity_check": bad == 0,
-        "parity_detail": {"sample": sample, "rounds": it, "mismatches": bad,
-                          "oracle": "oracle.lr_apply, bit-exact restatement pinned by tests/golden/lr_ref.npz"},
+        "parity_check": None if bad is None else bad == 0,
         "roofline": roofline(per * n, kernel_ms, args, "k_lr_apply_sum<ADAM> (merge + Adam, one launch)", 4),
         "event_markers": ("timing-only (hipEventDisableSystemFence)" if TIMING_EVENTS
                           else "default (system-scope fence at each record)"),
-        "copy_ceiling": {"kernel": "k_lr_apply_sum<ADAM, COPY> (psg_lr_mix_copy): the same loads and stores "
-                                   "with a copy's arithmetic",
-                         "ms": round(copy_ms, 5),
-                         "gbs": round(per * n / (copy_ms * 1e-3) / 1e9, 1),
-                         "frac": round(per * n / (copy_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "adam_of_copy": round(copy_ms / kernel_ms, 4)},
     }
-    if not args.no_cpu_baseline:
+    if full:
+        res["parity_detail"] = {"sample": sample, "rounds": it, "mismatches": bad,
+                                "oracle": "oracle.lr_apply, bit-exact restatement pinned by tests/golden/lr_ref.npz"}
+        res["copy_ceiling"] = {"kernel": "k_lr_apply_sum<ADAM, COPY> (psg_lr_mix_copy): the same loads and stores "
+                                         "with a copy's arithmetic",
+                               "ms": round(copy_ms, 5),
+                               "gbs": round(per * n / (copy_ms * 1e-3) / 1e9, 1),
+                               "frac": round(per * n / (copy_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                               "adam_of_copy": round(copy_ms / kernel_ms, 4)}
+    if full and not args.no_cpu_baseline:
+        import oracle
         # the same round restated in oracle/ on one core, on a bounded sample
         cn = min(n, args.cpu_lr_features)
         rng = np.random.default_rng(args.seed)
@@ -1372,7 +1436,7 @@ def run_dropin(args, n_gpus: int) -> dict:
                ("fused", "ident", "runs", "run_frames", "strided_runs", "strided_frames", "strided_single")}
         tot["requests"] = N * N * 2 * (args.warmup + args.steps)
         res["server_counters"] = tot
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle
         t0 = time.perf_counter()
         f0, p0, l0 = oracle.bench(min(n, args.cpu_configs0_keys or n), 6)
@@ -1500,6 +1564,14 @@ def main(argv=None) -> None:
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="dense")
     ap.add_argument("--keys", type=int, default=None, help="values per worker (default by workload)")
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity check against the "
+                         "closed form and the oracle, the 256 M / batched / accumulate / copy-ceiling "
+                         "probes and the CPU baseline (--check, --no-probe256, --no-cpu-baseline and "
+                         "the --cpu-* sizes apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to DIR/<name>.npy "
+                         "(float32; an output of more than 4 Mi values as a fixed seeded sample)")
     ap.add_argument("--check", type=int, default=1)
     ap.add_argument("--event-every", type=int, default=10,
                     help="record the kernel-timing HIP events on every n-th timed step")
@@ -1535,6 +1607,9 @@ def main(argv=None) -> None:
         # the job launches its own nodes (one per GPU): run it from one process
         if world > 1:
             raise SystemExit("--workload dropin launches its own ns = nw = --gpus nodes: run it as one process")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the drop-in job's nodes are processes of their own, whose pulled "
+                             "vectors this process never holds; every worker checks its own (parity_check)")
         print(json.dumps(run_dropin(args, args.gpus)), flush=True)
         return
     group = None

@@ -42,7 +42,7 @@ def test_configs2_n8_256m_per_worker_shared_gpu():
     env = dict(os.environ, PSG_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--keys", str(256 << 20),
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--keys", str(256 << 20),
            "--steps", "3", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -60,7 +60,7 @@ def test_configs4_f16_1g_dense():
     import argparse
     import bench
     args = argparse.Namespace(keys=1 << 30, seed=7, warmup=1, steps=3, check=1, event_every=1,
-                              no_cpu_baseline=True, no_probe256=True, workload="dense-f16")
+                              no_cpu_baseline=True, no_probe256=True, workload="dense-f16", full=True)
     res = bench.run(bench.GpuBackend(0, 1, 0, None, "f16"), args, 0, 1)
     assert res["parity_check"] is True, res
     assert res["parity_detail"]["device_mismatches"] == 0 and res["parity_detail"]["elements"] == 1 << 30
@@ -114,7 +114,7 @@ def _bench_shared(nranks, extra, env_extra, timeout=600):
     env = dict(os.environ, PSG_BENCH_SHARE_GPU="1", **env_extra)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks),
            "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(nranks)] + extra
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(nranks)] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -183,7 +183,8 @@ def test_keyed_bench_line_store_layouts(env_extra, coded):
     where the tiles are 1024-thread ones — at least every other store key —
     (psg_store_counters), and the roofline names the kernels that ran."""
     env = dict(os.environ, **env_extra)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "keyed", "--keys", "2000000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "keyed", "--keys",
+                        "2000000",
                         "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--no-probe256"],
                        capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

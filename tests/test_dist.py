@@ -103,7 +103,7 @@ def _rank_main(rank, world, port, outdir):
     # bench.py's own torch-free rendezvous orchestrates; gloo carries only this
     # backend's data (the collectives RCCL carries on the GPU)
     group = SocketGroup(rank, world, path=os.path.join(outdir, "rdzv"))
-    args = argparse.Namespace(keys=12288, seed=7, warmup=1, steps=3, check=1, no_cpu_baseline=True)
+    args = argparse.Namespace(keys=12288, seed=7, warmup=1, steps=3, check=1, no_cpu_baseline=True, full=True)
     res = bench.run(CpuCollectiveBackend(rank, world, dist), args, rank, world, group)
     with open(os.path.join(outdir, f"r{rank}.json"), "w") as f:
         json.dump(res, f)

@@ -2,9 +2,9 @@
 run on the MI355X: KVServerDefaultHandle<float> keeps its store in HBM and
 answers every request with the psg kernels.
 
-The binaries are built in the build container from /root/reference/tests
-(`make -C parameter-server_amd dropin`) and travel to the GPU box as build
-products; the reference sources never do.  test_kv_app.cpp and
+The binaries are built where the reference tree exists
+(`make -C parameter-server_amd dropin`, into oracle/_ref/) and travel with the
+tree as build products; the reference sources never do.  test_kv_app.cpp and
 test_kv_app_multi_workers.cpp CHECK their known answers themselves (a failed
 CHECK aborts the job, non-zero exit).
 """
@@ -18,7 +18,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DROPIN = os.path.join(ROOT, "tests", "_dropin")
+DROPIN = os.path.join(ROOT, "oracle", "_ref")
 BIN = os.path.join(ROOT, "tests", "_bin")
 
 

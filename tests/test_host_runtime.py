@@ -2,7 +2,7 @@
 
 tests/_bin/kv_cluster_host runs real KVWorker / KVServer nodes with a host
 request handle (test code), so no GPU is needed.  The reference's own harnesses
-compiled unmodified against the runtime live in tests/_dropin/ (built by
+compiled unmodified against the runtime live in oracle/_ref/ (built by
 `make -C parameter-server_amd dropin` where the reference tree exists).
 """
 import os
@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "tests", "_bin")
-DROPIN = os.path.join(ROOT, "tests", "_dropin")
+DROPIN = os.path.join(ROOT, "oracle", "_ref")
 
 
 def run(path, *args, timeout=120, env=None):
@@ -221,24 +221,52 @@ def test_group_broadcast(procs):
     assert r.stdout.count("bcast ok") == 6
 
 
-REF_LOCAL_PY = "/root/reference/tests/local.py"
+REF_LOCAL_LAUNCH = os.path.join(ROOT, "tests", "golden", "ref_local_launch.json")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_LOCAL_PY), reason="reference tree absent (GPU box)")
+def _free_port():
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
 def test_reference_local_py_launches_our_binaries(tmp_path):
-    """The reference's own launcher (tests/local.py, run where the reference
-    tree exists) starts our binaries unchanged: its `config log role` command
-    lines select process mode.  local.py ignores its children's exit codes, so
-    the check is on what the nodes print."""
-    import sys
+    """The reference's own launcher (tests/local.py -ns 2 -nw 2 -exec PROGRAM)
+    starts our binaries unchanged: its `config log role` command lines select
+    process mode.  The launch is replayed from a recording of what local.py
+    hands to each node (tests/golden/ref_local_launch.json: the arguments and
+    the config file it writes first), in its order and without waiting between
+    nodes; only the scheduler's port is this test's own (the recording's may
+    be taken on a shared machine).  local.py ignores its children's exit
+    codes, so the check is on what the nodes print."""
+    import json
+    with open(REF_LOCAL_LAUNCH) as f:
+        nodes = json.load(f)["nodes"]
+    assert [n["argv"][2] for n in nodes] == ["scheduler", "server", "server", "worker", "worker"]
     for exe, expect in [(os.path.join(BIN, "kv_cluster_host"), 2),
                         (os.path.join(DROPIN, "test_simple_app"), 0)]:
         _need(exe)
-        r = subprocess.run([sys.executable, REF_LOCAL_PY, "-ns", "2", "-nw", "2", "-exec", exe],
-                           cwd=tmp_path, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr[-2000:]
-        assert "Check failed" not in r.stderr and "aborted" not in r.stderr, r.stderr[-2000:]
-        assert r.stdout.count(" ok") == expect, r.stdout
+        port = _free_port()
+        procs = []
+        with open(tmp_path / "stdout.txt", "w+") as out, open(tmp_path / "stderr.txt", "w+") as err:
+            try:
+                for n in nodes:
+                    with open(tmp_path / n["argv"][0], "w") as f:
+                        json.dump(dict(n["config"], PS_SCHEDULER_PORT=port), f, indent=4)
+                    procs.append(subprocess.Popen([exe] + n["argv"], cwd=tmp_path, stdout=out, stderr=err))
+                for p in procs:
+                    p.wait(timeout=120)
+            finally:
+                for p in procs:
+                    if p.poll() is None:
+                        p.kill()
+                        p.wait()
+            out.seek(0)
+            err.seek(0)
+            stdout, stderr = out.read(), err.read()
+        assert "Check failed" not in stderr and "aborted" not in stderr, stderr[-2000:]
+        assert stdout.count(" ok") == expect, stdout
 
 
 def test_process_job_ends_when_a_node_dies():
@@ -311,12 +339,14 @@ def test_process_mode_refused_ring_falls_back_to_the_socket():
 def test_hung_process_job_prints_every_threads_stack():
     """PS_JOB_TIMEOUT_S: a process job still running at the deadline is taken
     as hung; every node prints the stacks of all its threads (SIGQUIT), then
-    the launcher kills the job and exits 124.  A 3 M-key job with a 1 s limit
-    stands in for a hang."""
+    the launcher kills the job and exits 124.  A 30 M-key job with a 1 s limit
+    stands in for a hang: the launcher asks the five nodes one at a time, 0.5 s
+    apart, so the job must still be running 3.5 s after its start (a 3 M-key
+    job is over by then on a fast host, and its workers print nothing)."""
     exe = os.path.join(BIN, "kv_cluster_host")
     _need(exe)
     e = dict(os.environ, PS_JOB_TIMEOUT_S="1")
-    r = subprocess.run([exe, "-ns", "2", "-nw", "2", "-procs", "3000000"], capture_output=True, text=True,
+    r = subprocess.run([exe, "-ns", "2", "-nw", "2", "-procs", "30000000"], capture_output=True, text=True,
                        timeout=60, env=e)
     assert r.returncode == 124, r.stderr[-2000:]
     assert "PS_JOB_TIMEOUT_S=1" in r.stderr

@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "_dropin", "LR_ps")
+EXE = os.path.join(ROOT, "oracle", "_ref", "LR_ps")
 NF, NW, ITERS = 123, 4, 6
 
 

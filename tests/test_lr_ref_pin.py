@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "_dropin", "lr_ref_pin")
+EXE = os.path.join(ROOT, "oracle", "_ref", "lr_ref_pin")
 LR = 0.01
 EPOCHS, BATCHES = 3, 4
 

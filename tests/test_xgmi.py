@@ -157,7 +157,7 @@ def test_bench_shared_gpu_xgmi_verified(nproc, exchange):
     keys = 3 * (1 << 20) + 3 * 4 * 37 if nproc == 3 else 1 << 22
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--keys", str(keys),
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(nproc), "--keys", str(keys),
            "--steps", "3", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -13,9 +13,9 @@
 #     VARIANT  an env assignment list ("" = defaults); -procs / -ns N in a
 #              variant are appended to the command instead
 # examples (the round-5 one-offs):
-#   keyed lines            bash tools/ab.sh gpurun_out/k.txt 2 'grep:^{:python3 bench.py --workload keyed --steps 30 --warmup 5 --no-cpu-baseline --no-probe256' "" "PSG_RA_MIDENT=0"
+#   keyed lines            bash tools/ab.sh OUT/k.txt 2 'grep:^{:python3 bench.py --full --workload keyed --steps 30 --warmup 5 --no-cpu-baseline --no-probe256' "" "PSG_RA_MIDENT=0"
 #   drop-in line, N = 1    bash tools/ab.sh gpurun_out/d.txt 2 'grep:rank:tests/_bin/kv_bench_dropin -ns 1 -nw 1 10000000 30 5 0' "" "-procs"
-#   configs[0] stages      bash tools/ab.sh gpurun_out/s.txt 2 'PS_STAGE_TIMES=1 tests/_dropin/test_kv_app_benchmark -ns 1 -nw 1' "" "-procs PS_SHM_ARENA_MB=0"
+#   configs[0] stages      bash tools/ab.sh OUT/s.txt 2 'PS_STAGE_TIMES=1 oracle/_ref/test_kv_app_benchmark -ns 1 -nw 1' "" "-procs PS_SHM_ARENA_MB=0"
 #   kernel stats           bash tools/ab.sh gpurun_out/p 1 'prof:python3 tools/pmc_targets.py frames8 10' "PSG_FRAMES_BPC=2" "PSG_FRAMES_BPC=8"
 # Every run has its own time limit (AB_TIMEOUT, default 300 s); a crash or a
 # time-out ends the script (no later GPU step runs).

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Find the BSP round at which the HBM LR handle's model first goes wrong.
 
-Runs tests/_dropin/lr_ref_pin in gpu mode (3 workers, 200,000 features, SGD,
+Runs oracle/_ref/lr_ref_pin in gpu mode (3 workers, 200,000 features, SGD,
 BSP, dyadic gradients — the case GPUTEST_r03 caught) with PIN_TRACE, so worker
 0 prints the last TRACE features of every Pull reply: the model after each
 round.  Against the oracle's trajectory (oracle.lr_apply, the restatement the
