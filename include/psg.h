@@ -15,6 +15,9 @@
  *   psg_store_handle the per-request accumulate loop
  *                    `store[key] += vals[i]; res.vals[i] = store[key]`
  *                                                        src/ps/KVApp.h:446-454
+ *   psg_table_*      the same store and loop for requests carrying k values
+ *                    per key (rows), as DefaultSlicer slices them
+ *                                                        src/ps/KVApp.h:515-574
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
  *   psg_slice        KVWorker<V>::DefaultSlicer           src/ps/KVApp.h:515-574
  *   psg_merge        the AddPullCB merge lambda           src/ps/KVApp.h:673-726
@@ -426,6 +429,62 @@ int psg_key_list_hash(const uint64_t* keys, uint64_t n, uint64_t* hash_host, psg
  * tests/src/LRServer.h:107-115).  keys_host may be NULL for a DENSE store;
  * both arrays must hold info.size elements.  Synchronous. */
 int psg_store_dump(psg_store* s, uint64_t* keys_host, void* vals_host);
+
+/* ======================================================================== */
+/* Row-valued table: a fixed-width vector per key                             */
+/* ======================================================================== */
+/* The row-valued counterpart of a PSG_STORE_SORTED store: arbitrary uint64
+ * keys in [key_begin, key_end), each holding a row of `width` elements of one
+ * dtype (an embedding row), kept as a sorted key array plus a row array in HBM
+ * in the same order.  A worker already slices k = vals.size() / keys.size()
+ * values per key (KVApp.h:515-574); this is the server side that keeps them.
+ * Calls on one table are serialised by the caller, as for a store. */
+typedef struct psg_table psg_table;
+typedef struct psg_table_info {
+  int dtype;
+  uint32_t width;      /* elements per row */
+  uint64_t key_begin;  /* owned key range [key_begin, key_end) */
+  uint64_t key_end;
+  uint64_t size;       /* keys (rows) currently present */
+  uint64_t capacity;   /* rows allocated */
+  void* rows;          /* device pointer to the row array (key order), size x width */
+  uint64_t* keys;      /* device pointer to the sorted key array */
+} psg_table_info;
+
+/* The store of the accumulate loop (src/ps/KVApp.h:446-454) for requests carrying
+ * `width` values per key (the k-values-per-key contract of KVApp.h:515-574).
+ * 1 <= width <= 4096; dtype one of PSG_F32 / F64 / F16 / BF16; capacity: rows
+ * to allocate at once (0: on first use; it grows x2).  At most 2^32-2 rows.
+ * Bad arguments fail with PSG_ERR_INVALID before any device call. */
+int psg_table_create(int dtype, uint32_t width, uint64_t key_begin, uint64_t key_end,
+                     uint64_t capacity, psg_table** out);
+/* Frees the store of src/ps/KVApp.h:446-454 (k values per key, KVApp.h:515-574). */
+int psg_table_destroy(psg_table* t);
+/* The table of src/ps/KVApp.h:446-454 (k values per key, KVApp.h:515-574) as it is now. */
+int psg_table_get_info(psg_table* t, psg_table_info* info);
+/* Drop every key (an empty `store` of src/ps/KVApp.h:446-454; rows of k values per
+ * key, KVApp.h:515-574). */
+int psg_table_clear(psg_table* t, psg_stream stream);
+/* One request, the loop of src/ps/KVApp.h:446-454 on the k = width values per key a
+ * worker slices (KVApp.h:515-574):
+ *   for i < n, j < width:  if (flags & PSG_PUSH) row(key_i)[j] += vals[i*width + j];
+ *                          if (flags & PSG_PULL) out[i*width + j] = row(key_i)[j];  (post-update)
+ * keys: n device keys, strictly ascending (the KVPairs contract, KVApp.h:23);
+ * vals / out: device arrays of n * width elements of the table's dtype.  Each
+ * add is rounded to the dtype as psg_store_handle rounds it.  An absent key
+ * is inserted with a zero row, on a Push and on a Pull (operator[]).  Keys out
+ * of order or repeated fail the request with PSG_ERR_INVALID, a key outside
+ * the range with PSG_ERR_RANGE; every key is checked before the first write,
+ * so a request that fails leaves the table bit for bit unchanged (the
+ * order-preserving path psg_store_handle has for such lists is not built for
+ * rows).  Returns as psg_store_handle does: keys and vals are no longer read
+ * and a Pull's reply is in memory.  n == 0 is a no-op. */
+int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* vals,
+                     void* out, uint64_t n, psg_stream stream);
+/* Copy the table (src/ps/KVApp.h:446-454's store, k values per key, KVApp.h:515-574)
+ * to host memory in key order: info.size keys (keys_host may be NULL) and
+ * info.size * width elements.  Synchronous. */
+int psg_table_dump(psg_table* t, uint64_t* keys_host, void* rows_host);
 
 /* ======================================================================== */
 /* Worker side: key-range slicing and pull merge                              */

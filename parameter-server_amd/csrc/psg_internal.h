@@ -146,6 +146,40 @@ __device__ __forceinline__ uint64_t lower_bound_wave(const uint64_t* __restrict_
   const bool pred = p < hi && a[p] < key;
   return lo + (uint64_t)__popcll(__ballot(pred));
 }
+
+// lower_bound by one lane over a[lo, hi).
+__device__ __forceinline__ uint64_t lower_bound_dev(const uint64_t* __restrict__ a, uint64_t lo,
+                                                    uint64_t hi, uint64_t key) {
+  while (lo < hi) {
+    uint64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Block-wide exclusive scan helper over 256 lanes (wave = 64).
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total) {
+  __shared__ uint32_t wsum[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    uint32_t y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) wsum[w] = x;
+  __syncthreads();
+  uint32_t off = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k < w) off += wsum[k];
+    tot += wsum[k];
+  }
+  __syncthreads();
+  *total = tot;
+  return off + x - v;
+}
 #endif
 
 // Bytes to hipMalloc for an array a peer process may map (hipIpc): the HIP

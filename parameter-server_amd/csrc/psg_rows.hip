@@ -1,0 +1,520 @@
+// psg_rows.hip — the row-valued HBM table (psg_table_*): arbitrary uint64 keys,
+// each holding a row of `width` elements of one dtype.
+//
+// Reference: the same server loop as the scalar store, KVServerDefaultHandle
+// (src/ps/KVApp.h:446-454), applied to the k = vals.size() / keys.size() values
+// a worker slices per key (DefaultSlicer, src/ps/KVApp.h:515-574):
+//     for j < width:  row(key_i)[j] += vals[i * width + j];
+//                     out[i * width + j] = row(key_i)[j];
+//
+// Layout: a sorted key array K[S] and the rows in the same order in one array
+// R[S x width]; growth x2; an insert is a merge into new arrays that moves
+// whole rows (the width-wide analogue of psg_store.hip's merge_insert).
+//
+// A request is two passes with the host between them:
+//   k_rows_resolve   reads each key once: strict ascent against its
+//                    predecessor, the range, its place in K (a search inside
+//                    the stretch of K its 1024-key tile spans) -> a uint32 slot
+//                    (UINT32_MAX: absent) and the request flags.  The host
+//                    reads the flags (one synchronisation), rejects the request
+//                    before anything was written, or inserts the absent keys
+//                    and resolves again.
+//   k_rows_apply     the rows: lanes run over a tile's rows as one flat stream
+//                    of 16-B vectors (rows of a multiple of 16 B) or of single
+//                    elements, so consecutive slots read and write consecutive
+//                    memory; one writer per row (keys are unique): no atomics.
+// Algorithmic bytes per f32 key of a Push: key 8 + slot 4 + 4 + 12 * width.
+#include <algorithm>
+#include <cstring>
+
+#include "psg_internal.h"
+
+struct psg_table {
+  int dtype;
+  int esize;
+  uint32_t width;
+  uint64_t key_begin, key_end;
+  uint64_t size;      // rows present
+  uint64_t capacity;  // rows allocated
+  void* rows;         // device, capacity * width * esize
+  uint64_t* keys;     // device, capacity
+  uint32_t* slots;    // device scratch: the request's slots
+  uint64_t slots_cap;
+  int* flags;       // device view of flags_host
+  int* flags_host;  // pinned host int[kNFlags], raised by k_rows_resolve
+};
+
+namespace psg {
+namespace {
+
+constexpr int kRowTile = 1024;  // request keys per block of the resolve (4 per lane)
+constexpr uint32_t kAbsent = 0xffffffffu;
+constexpr uint64_t kMaxRows = 0xfffffffeull;
+// vectors (or elements) one block of k_rows_apply / k_rows_move serves per tile
+constexpr uint32_t kUnitsPerTile = 2048;
+constexpr int kUnroll = 4;  // loads a lane keeps in flight
+
+enum { R_MISSING = 0, R_RANGE = 1, R_UNSORTED = 2, kNFlags = 4 };
+
+__device__ __forceinline__ void raise(int* flags, int which, bool cond) {
+  if (__ballot(cond) && (threadIdx.x & 63) == 0) flags[which] = 1;
+}
+
+// Pass 1.  Tile = 1024 request keys; waves 0 and 1 bracket the tile's keys in
+// K (lower_bound_wave of its first and last key), every lane then searches only
+// that stretch: ~10 steps over lines its neighbours share when the request
+// covers a stretch of the table.  A list out of order gives a meaningless (but
+// in-bounds) bracket; its request is rejected by the flags.
+__global__ __launch_bounds__(256) void k_rows_resolve(const uint64_t* __restrict__ q, uint64_t n,
+                                                      const uint64_t* __restrict__ K, uint64_t S, uint64_t kb,
+                                                      uint64_t ke, uint32_t* __restrict__ slots,
+                                                      int* __restrict__ flags) {
+  __shared__ uint64_t win[2];
+  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  int missing = 0, range = 0, unsorted = 0;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t t0 = t * kRowTile;
+    const uint64_t t1 = t0 + kRowTile < n ? t0 + kRowTile : n;
+    const int w = threadIdx.x >> 6;
+    if (w == 0) {
+      const uint64_t lo = lower_bound_wave(K, S, q[t0]);
+      if ((threadIdx.x & 63) == 0) win[0] = lo;
+    } else if (w == 1) {
+      uint64_t hi = lower_bound_wave(K, S, q[t1 - 1]);
+      hi = hi < S ? hi + 1 : S;
+      if ((threadIdx.x & 63) == 0) win[1] = hi;
+    }
+    __syncthreads();
+    const uint64_t lo = win[0];
+    const uint64_t hi = win[1] > lo ? win[1] : lo;
+#pragma unroll
+    for (int k = 0; k < kRowTile / kBlock; ++k) {
+      const uint64_t i = t0 + (uint64_t)k * kBlock + threadIdx.x;
+      if (i >= t1) continue;
+      const uint64_t key = q[i];
+      if (i > 0 && q[i - 1] >= key) unsorted = 1;
+      if (key < kb || key >= ke) range = 1;
+      const uint64_t p = lower_bound_dev(K, lo, hi, key);
+      const bool found = p < S && K[p] == key;
+      if (!found) missing = 1;
+      slots[i] = found ? (uint32_t)p : kAbsent;
+    }
+    __syncthreads();
+  }
+  raise(flags, R_MISSING, missing != 0);
+  raise(flags, R_RANGE, range != 0);
+  raise(flags, R_UNSORTED, unsorted != 0);
+}
+
+// ---- absent keys, in order, into miss[] (counts per tile, scan, compaction) ----
+__global__ __launch_bounds__(256) void k_rows_tile_missing(const uint32_t* __restrict__ slots, uint64_t n,
+                                                           uint32_t* __restrict__ counts) {
+  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kRowTile / kBlock; ++k)
+    if (i0 + k < n && slots[i0 + k] == kAbsent) c++;
+  uint32_t tot;
+  block_excl_scan(c, &tot);
+  if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void k_rows_scan_counts(uint32_t* __restrict__ counts, uint64_t ntiles) {
+  __shared__ uint32_t carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (uint64_t b = 0; b < ntiles; b += kBlock) {
+    const uint64_t i = b + threadIdx.x;
+    const uint32_t v = i < ntiles ? counts[i] : 0;
+    uint32_t tot;
+    const uint32_t ex = block_excl_scan(v, &tot);
+    if (i < ntiles) counts[i] = carry + ex;
+    __syncthreads();
+    if (threadIdx.x == 0) carry += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) counts[ntiles] = carry;  // the total: keys absent
+}
+
+__global__ __launch_bounds__(256) void k_rows_compact_missing(const uint64_t* __restrict__ q,
+                                                              const uint32_t* __restrict__ slots, uint64_t n,
+                                                              const uint32_t* __restrict__ offs,
+                                                              uint64_t* __restrict__ miss) {
+  // each lane owns 4 consecutive keys so the order inside the tile is kept
+  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kRowTile / kBlock; ++k)
+    if (i0 + k < n && slots[i0 + k] == kAbsent) c++;
+  uint32_t tot;
+  uint32_t pos = offs[blockIdx.x] + block_excl_scan(c, &tot);
+#pragma unroll
+  for (int k = 0; k < kRowTile / kBlock; ++k)
+    if (i0 + k < n && slots[i0 + k] == kAbsent) miss[pos++] = q[i0 + k];
+}
+
+// Merge, keys: old row j goes to j + #(new keys < K[j]), new key t to
+// t + #(old keys < M[t]); the places are kept (old_to / new_to) for the rows.
+__global__ __launch_bounds__(256) void k_rows_merge_keys(const uint64_t* __restrict__ K, uint64_t S,
+                                                         const uint64_t* __restrict__ M, uint64_t m,
+                                                         uint64_t* __restrict__ K2, uint32_t* __restrict__ old_to,
+                                                         uint32_t* __restrict__ new_to) {
+  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < S + m; j += (uint64_t)gridDim.x * kBlock) {
+    if (j < S) {
+      const uint64_t key = K[j];
+      const uint64_t d = j + lower_bound_dev(M, 0, m, key);
+      K2[d] = key;
+      old_to[j] = (uint32_t)d;
+    } else {
+      const uint64_t t = j - S;
+      const uint64_t key = M[t];
+      const uint64_t d = t + lower_bound_dev(K, 0, S, key);
+      K2[d] = key;
+      new_to[t] = (uint32_t)d;
+    }
+  }
+}
+
+// A lane's walk over a tile of rows as one flat stream of units (16-B vectors
+// or elements), `upr` units a row: unit e is column e % upr of row e / upr.
+// One division at the start, then steps of kBlock units.
+struct RowWalk {
+  uint32_t r, c, dr, dc, upr;
+  __device__ __forceinline__ RowWalk(uint32_t e, uint32_t units_per_row)
+      : r(e / units_per_row), c(e - r * units_per_row), dr(kBlock / units_per_row),
+        dc(kBlock - dr * units_per_row), upr(units_per_row) {}
+  __device__ __forceinline__ void next() {
+    r += dr;
+    c += dc;
+    if (c >= upr) {
+      c -= upr;
+      ++r;
+    }
+  }
+};
+
+// rows per tile, so that a tile holds about kUnitsPerTile units (at least one row)
+inline uint32_t rows_per_tile(uint32_t upr) { return upr >= kUnitsPerTile ? 1u : kUnitsPerTile / upr; }
+
+// Merge, rows: dst row to[j] = src row j (src == nullptr: a zero row), for j < nrows.
+template <typename U>
+__global__ __launch_bounds__(256) void k_rows_move(const U* __restrict__ src, U* __restrict__ dst,
+                                                   const uint32_t* __restrict__ to, uint64_t nrows, uint32_t upr,
+                                                   uint32_t rpt) {
+  const uint64_t ntiles = (nrows + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t j0 = t * rpt;
+    const uint32_t nr = (uint32_t)(nrows - j0 < rpt ? nrows - j0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
+      const uint64_t j = j0 + w.r;
+      U v = {};
+      if (src) v = src[j * upr + w.c];
+      dst[(uint64_t)to[j] * upr + w.c] = v;
+    }
+  }
+}
+
+template <int DT, bool VEC> struct Unit;
+template <int DT> struct Unit<DT, true> {
+  typedef u32x4 U;
+  __device__ static inline U add(U a, U b) { return Elem<DT>::add(a, b); }
+};
+template <int DT> struct Unit<DT, false> {
+  typedef typename Elem<DT>::T U;
+  __device__ static inline U add(U a, U b) { return Elem<DT>::add1(a, b); }
+};
+
+// Pass 2.  Request row i (slot slots[i]) for i < n; every slot is present.
+template <int DT, int OP, bool VEC>
+__global__ __launch_bounds__(256) void k_rows_apply(typename Unit<DT, VEC>::U* __restrict__ R,
+                                                    const uint32_t* __restrict__ slots,
+                                                    const typename Unit<DT, VEC>::U* __restrict__ vals,
+                                                    typename Unit<DT, VEC>::U* __restrict__ out, uint64_t n,
+                                                    uint32_t upr, uint32_t rpt) {
+  using UT = Unit<DT, VEC>;
+  using U = typename UT::U;
+  const uint64_t ntiles = (n + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t i0 = t * rpt;
+    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += kUnroll * kBlock) {
+      uint64_t so[kUnroll], ro[kUnroll];
+      bool ok[kUnroll];
+      U s[kUnroll], v[kUnroll];
+#pragma unroll
+      for (int k = 0; k < kUnroll; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t i = i0 + w.r;
+          so[k] = (uint64_t)slots[i] * upr + w.c;
+          ro[k] = i * upr + w.c;
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < kUnroll; ++k) {
+        if (!ok[k]) continue;
+        s[k] = R[so[k]];
+        if constexpr ((OP & PSG_PUSH) != 0) v[k] = vals[ro[k]];
+      }
+#pragma unroll
+      for (int k = 0; k < kUnroll; ++k) {
+        if (!ok[k]) continue;
+        if constexpr ((OP & PSG_PUSH) != 0) {
+          s[k] = UT::add(s[k], v[k]);
+          R[so[k]] = s[k];
+        }
+        if constexpr ((OP & PSG_PULL) != 0) out[ro[k]] = s[k];
+      }
+    }
+  }
+}
+
+unsigned grid_for(uint64_t blocks) {
+  const uint64_t cap = (uint64_t)max_stream_blocks();
+  if (blocks > cap) blocks = cap;
+  return blocks ? (unsigned)blocks : 1u;
+}
+
+template <int DT, bool VEC>
+int launch_apply(psg_table* t, int op, const void* vals, void* out, uint64_t n, hipStream_t st) {
+  using U = typename Unit<DT, VEC>::U;
+  const uint32_t upr = VEC ? t->width / Elem<DT>::kVec : t->width;
+  const uint32_t rpt = rows_per_tile(upr);
+  const unsigned g = grid_for((n + rpt - 1) / rpt);
+  U* R = (U*)t->rows;
+  switch (op) {
+    case PSG_PUSH:
+      k_rows_apply<DT, PSG_PUSH, VEC><<<g, kBlock, 0, st>>>(R, t->slots, (const U*)vals, (U*)out, n, upr, rpt);
+      break;
+    case PSG_PULL:
+      k_rows_apply<DT, PSG_PULL, VEC><<<g, kBlock, 0, st>>>(R, t->slots, (const U*)vals, (U*)out, n, upr, rpt);
+      break;
+    default:
+      k_rows_apply<DT, PSG_PUSH | PSG_PULL, VEC><<<g, kBlock, 0, st>>>(R, t->slots, (const U*)vals, (U*)out, n, upr,
+                                                                      rpt);
+  }
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+template <int DT>
+int apply_dtype(psg_table* t, int op, const void* vals, void* out, uint64_t n, hipStream_t st) {
+  // 16-B vectors when every row, here and in the request, starts on 16 B
+  const bool vec = ((uint64_t)t->width * t->esize) % 16 == 0 && (!(op & PSG_PUSH) || aligned16(vals)) &&
+                   (!(op & PSG_PULL) || aligned16(out));
+  return vec ? launch_apply<DT, true>(t, op, vals, out, n, st) : launch_apply<DT, false>(t, op, vals, out, n, st);
+}
+
+int apply(psg_table* t, int op, const void* vals, void* out, uint64_t n, hipStream_t st) {
+  switch (t->dtype) {
+    case PSG_F32: return apply_dtype<PSG_F32>(t, op, vals, out, n, st);
+    case PSG_F64: return apply_dtype<PSG_F64>(t, op, vals, out, n, st);
+    case PSG_F16: return apply_dtype<PSG_F16>(t, op, vals, out, n, st);
+    default: return apply_dtype<PSG_BF16>(t, op, vals, out, n, st);
+  }
+}
+
+template <typename U>
+int launch_move(const void* src, void* dst, const uint32_t* to, uint64_t nrows, uint32_t upr, hipStream_t st) {
+  const uint32_t rpt = rows_per_tile(upr);
+  k_rows_move<U><<<grid_for((nrows + rpt - 1) / rpt), kBlock, 0, st>>>((const U*)src, (U*)dst, to, nrows, upr, rpt);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+// rows move as raw bytes: 16-B, 4-B or 2-B units, whichever the row length allows
+int move_rows(const psg_table* t, const void* src, void* dst, const uint32_t* to, uint64_t nrows, hipStream_t st) {
+  const uint32_t rb = t->width * (uint32_t)t->esize;
+  if (rb % 16 == 0) return launch_move<u32x4>(src, dst, to, nrows, rb / 16, st);
+  if (rb % 4 == 0) return launch_move<uint32_t>(src, dst, to, nrows, rb / 4, st);
+  return launch_move<uint16_t>(src, dst, to, nrows, rb / 2, st);
+}
+
+int ensure_slots(psg_table* t, uint64_t n) {
+  if (t->slots_cap >= n) return PSG_OK;
+  if (t->slots) PSG_HIP(hipFree(t->slots));
+  t->slots = nullptr;
+  t->slots_cap = 0;
+  const uint64_t cap = std::max<uint64_t>(n, 1 << 16);
+  PSG_HIP(hipMalloc((void**)&t->slots, cap * sizeof(uint32_t)));
+  t->slots_cap = cap;
+  return PSG_OK;
+}
+
+// Launch the resolve of q into t->slots and wait for its flags.
+int resolve(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) {
+  memset(t->flags_host, 0, kNFlags * sizeof(int));
+  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  k_rows_resolve<<<grid_for(ntiles), kBlock, 0, st>>>(q, n, t->keys, t->size, t->key_begin, t->key_end, t->slots,
+                                                      t->flags);
+  PSG_HIP(hipGetLastError());
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+struct DevBuf {  // a device scratch array freed on every return path
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// Insert the keys of q that t->slots marks absent, each with a zero row.
+int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) {
+  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  DevBuf counts, miss, old_to, new_to;
+  PSG_HIP(hipMalloc(&counts.p, (ntiles + 1) * sizeof(uint32_t)));
+  k_rows_tile_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(t->slots, n, (uint32_t*)counts.p);
+  k_rows_scan_counts<<<1, kBlock, 0, st>>>((uint32_t*)counts.p, ntiles);
+  PSG_HIP(hipGetLastError());
+  uint32_t m32 = 0;
+  PSG_HIP(hipMemcpyAsync(&m32, (uint32_t*)counts.p + ntiles, sizeof(m32), hipMemcpyDeviceToHost, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  const uint64_t m = m32, S = t->size;
+  if (m == 0) return PSG_OK;
+  uint64_t cap = t->capacity;
+  if (S + m > cap) cap = std::max<uint64_t>(std::max<uint64_t>(S + m, cap * 2), 1024);
+  if (cap > kMaxRows) cap = kMaxRows;
+  PSG_REQUIRE(S + m <= kMaxRows, PSG_ERR_RANGE, "psg_table: more than 2^32-2 rows");
+  const uint64_t row_bytes = (uint64_t)t->width * t->esize;
+  PSG_HIP(hipMalloc(&miss.p, m * sizeof(uint64_t)));
+  PSG_HIP(hipMalloc(&old_to.p, std::max<uint64_t>(S, 1) * sizeof(uint32_t)));
+  PSG_HIP(hipMalloc(&new_to.p, m * sizeof(uint32_t)));
+  k_rows_compact_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(q, t->slots, n, (const uint32_t*)counts.p,
+                                                              (uint64_t*)miss.p);
+  PSG_HIP(hipGetLastError());
+  DevBuf K2, R2;
+  PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
+  PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
+  k_rows_merge_keys<<<grid_for((S + m + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+      t->keys, S, (const uint64_t*)miss.p, m, (uint64_t*)K2.p, (uint32_t*)old_to.p, (uint32_t*)new_to.p);
+  PSG_HIP(hipGetLastError());
+  if (S) PSG_TRY(move_rows(t, t->rows, R2.p, (const uint32_t*)old_to.p, S, st));
+  PSG_TRY(move_rows(t, nullptr, R2.p, (const uint32_t*)new_to.p, m, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  void* old_keys = t->keys;  // the old arrays are freed with K2 / R2
+  t->keys = (uint64_t*)K2.p;
+  K2.p = old_keys;
+  std::swap(R2.p, t->rows);
+  t->size = S + m;
+  t->capacity = cap;
+  return PSG_OK;
+}
+
+}  // namespace
+}  // namespace psg
+
+using namespace psg;
+
+extern "C" {
+
+int psg_table_create(int dtype, uint32_t width, uint64_t key_begin, uint64_t key_end, uint64_t capacity,
+                     psg_table** out) {
+  PSG_REQUIRE(out, PSG_ERR_INVALID, "psg_table_create: null out");
+  *out = nullptr;
+  const int es = dtype_size(dtype);
+  PSG_REQUIRE(es > 0, PSG_ERR_INVALID, "psg_table_create: bad dtype %d", dtype);
+  PSG_REQUIRE(width >= 1 && width <= 4096, PSG_ERR_INVALID, "psg_table_create: width %u outside [1, 4096]", width);
+  PSG_REQUIRE(key_begin < key_end, PSG_ERR_INVALID, "psg_table_create: empty key range");
+  PSG_REQUIRE(capacity <= kMaxRows, PSG_ERR_RANGE, "psg_table_create: capacity above 2^32-2 rows");
+  psg_table* t = new psg_table();  // value-initialised: every field zero
+  t->dtype = dtype;
+  t->esize = es;
+  t->width = width;
+  t->key_begin = key_begin;
+  t->key_end = key_end;
+  auto fail = [&](hipError_t e, const char* what) {
+    const int rc = hip_fail(e, what, __FILE__, __LINE__);
+    psg_table_destroy(t);
+    return rc;
+  };
+  hipError_t e;
+  if ((e = hipHostMalloc((void**)&t->flags_host, kNFlags * sizeof(int),
+                         hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
+    return fail(e, "hipHostMalloc(flags)");
+  if ((e = hipHostGetDevicePointer((void**)&t->flags, t->flags_host, 0)) != hipSuccess)
+    return fail(e, "hipHostGetDevicePointer(flags)");
+  if (capacity > 0) {
+    if ((e = hipMalloc((void**)&t->keys, capacity * sizeof(uint64_t))) != hipSuccess)
+      return fail(e, "hipMalloc(table keys)");
+    if ((e = hipMalloc(&t->rows, capacity * (uint64_t)width * es)) != hipSuccess)
+      return fail(e, "hipMalloc(table rows)");
+    t->capacity = capacity;
+  }
+  *out = t;
+  return PSG_OK;
+}
+
+int psg_table_destroy(psg_table* t) {
+  if (!t) return PSG_OK;
+  if (t->rows) (void)hipFree(t->rows);
+  if (t->keys) (void)hipFree(t->keys);
+  if (t->slots) (void)hipFree(t->slots);
+  if (t->flags_host) (void)hipHostFree(t->flags_host);
+  delete t;
+  return PSG_OK;
+}
+
+int psg_table_get_info(psg_table* t, psg_table_info* info) {
+  PSG_REQUIRE(t && info, PSG_ERR_INVALID, "psg_table_get_info: null argument");
+  info->dtype = t->dtype;
+  info->width = t->width;
+  info->key_begin = t->key_begin;
+  info->key_end = t->key_end;
+  info->size = t->size;
+  info->capacity = t->capacity;
+  info->rows = t->rows;
+  info->keys = t->keys;
+  return PSG_OK;
+}
+
+int psg_table_clear(psg_table* t, psg_stream stream) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_clear: null table");
+  (void)stream;  // every request has completed when its call returned: nothing to order behind
+  t->size = 0;
+  return PSG_OK;
+}
+
+int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* vals, void* out, uint64_t n,
+                     psg_stream stream) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_handle: null table");
+  PSG_REQUIRE(flags >= 1 && flags <= 3, PSG_ERR_INVALID, "psg_table_handle: bad flags %d", flags);
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_handle: null keys");
+  PSG_REQUIRE(!(flags & PSG_PUSH) || vals, PSG_ERR_INVALID, "push without vals");
+  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_handle: more than 2^32-2 keys in one request");
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(ensure_slots(t, n));
+  PSG_TRY(resolve(t, keys, n, st));
+  const int* f = t->flags_host;
+  PSG_REQUIRE(!f[R_UNSORTED], PSG_ERR_INVALID,
+              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
+  PSG_REQUIRE(!f[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
+              (unsigned long long)t->key_begin, (unsigned long long)t->key_end);
+  if (f[R_MISSING]) {
+    PSG_TRY(insert_missing(t, keys, n, st));
+    PSG_TRY(resolve(t, keys, n, st));
+    PSG_REQUIRE(!t->flags_host[R_MISSING], PSG_ERR_HIP, "psg_table_handle: a key is absent after its insert");
+  }
+  PSG_TRY(apply(t, flags, vals, out, n, st));
+  // complete on return: keys and vals no longer read, a Pull's reply in memory
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+int psg_table_dump(psg_table* t, uint64_t* keys_host, void* rows_host) {
+  PSG_REQUIRE(t && rows_host, PSG_ERR_INVALID, "psg_table_dump: null argument");
+  PSG_HIP(hipDeviceSynchronize());
+  if (t->size == 0) return PSG_OK;
+  PSG_HIP(hipMemcpy(rows_host, t->rows, t->size * (uint64_t)t->width * t->esize, hipMemcpyDeviceToHost));
+  if (keys_host) PSG_HIP(hipMemcpy(keys_host, t->keys, t->size * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PSG_OK;
+}
+
+}  // extern "C"

@@ -196,15 +196,7 @@ __device__ __forceinline__ void request_done(uint64_t after, const Arrival& a, u
   __hip_atomic_store(word, tag_bits | f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-__device__ __forceinline__ uint64_t lower_bound_dev(const uint64_t* __restrict__ a, uint64_t lo,
-                                                    uint64_t hi, uint64_t key) {
-  while (lo < hi) {
-    uint64_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
+// lower_bound_dev: psg_internal.h
 
 // spare elements after a store's keys: k_resolve_apply's 16-B LDS loads may
 // read 8 B past the last key
@@ -1815,28 +1807,7 @@ __global__ __launch_bounds__(256) void k_slots_stretch(const uint32_t* __restric
   raise_flag(flags, F_MISSING, bad != 0);
 }
 
-// Block-wide exclusive scan helper over 256 lanes (wave = 64).
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wsum[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k < w) off += wsum[k];
-    tot += wsum[k];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + x - v;
-}
+// block_excl_scan: psg_internal.h
 
 // Pass 1 of the compaction: absent-key count per 1024-key tile.
 __global__ __launch_bounds__(256) void k_tile_missing(const uint32_t* __restrict__ slots, uint64_t n,

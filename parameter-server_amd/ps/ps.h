@@ -8,6 +8,7 @@
 #include "internal/PostOffice.h"
 #include "ps/base.h"
 #include "ps/kv_app.h"
+#include "ps/row_handle.h"
 #include "ps/simple_app.h"
 
 namespace ps {

@@ -1,0 +1,85 @@
+// ps/row_handle.h — a server handle that keeps a row of `width` values per key
+// in HBM (embedding rows).
+//
+// Reference: KVServerDefaultHandle's loop (src/ps/KVApp.h:446-454) for the
+// requests a worker sends with k = vals.size() / keys.size() values per key,
+// which DefaultSlicer already slices per server (src/ps/KVApp.h:515-574) and
+// the pull merge concatenates; the reference's default handle CHECKs
+// n == vals.size() (KVApp.h:441) and so cannot keep them.
+//
+//   Push:  row(key_i)[j] += vals[i * width + j]
+//   Pull:  res.vals[i * width + j] = row(key_i)[j]    (post-update)
+//
+// The rows live in a psg_table over [0, kMaxKey), created on the first
+// request; an absent key is inserted with a zero row.  Keys must be strictly
+// ascending (the KVPairs contract, KVApp.h:23): a list out of order or with
+// repeats fails the request's CHECK, where the scalar default handle serves
+// it in arrival order.  Register with KVServer::SetDeviceRequestHandle, so
+// HBM frames are read in place; host frames are staged into HBM.  The handle
+// has no run handle: every request is served on its own, and workers slice
+// their key lists for real.
+#pragma once
+#include <memory>
+
+#include "ps/kv_app.h"
+
+namespace ps {
+
+template <typename Value>
+struct KVServerRowHandle {
+  struct State {
+    psg_table* table = nullptr;
+    uint32_t width = 0;
+    ~State() {
+      if (table) psg_table_destroy(table);
+    }
+  };
+  std::shared_ptr<State> state = std::make_shared<State>();
+
+  explicit KVServerRowHandle(uint32_t width) {
+    CHECK(width >= 1 && width <= 4096) << "KVServerRowHandle: width " << width << " outside [1, 4096]";
+    state->width = width;
+  }
+
+  void operator()(const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<Value>* server) {
+    const size_t n = req_data.keys.size();
+    const size_t w = state->width;
+    KVPairs<Value> res;
+    const int dev = PostOffice::Get()->device();
+    CHECK_GE(dev, 0) << "KVServerRowHandle: the table lives in HBM and this node has no GPU";
+    constexpr int dt = device::DType<Value>();
+    CHECK_GE(dt, 0) << "KVServerRowHandle: value type not supported by the HBM table";
+    CHECK(req_data.lens.empty()) << "KVServerRowHandle: rows have one fixed width, lens are not supported";
+    if (!state->table)
+      device::Check(psg_table_create(dt, state->width, 0, kMaxKey, 0, &state->table), "psg_table_create");
+    const bool on_dev = req_data.keys.on_device();
+    const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
+    if (req_meta.push) CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
+    SVector<Value> dout;
+    bool direct = false;
+    if (n && flags) {
+      psg_stream s = device::ThreadStream();
+      SVector<Key> dkeys = detail::ToDeviceAsync(req_data.keys, dev);
+      SVector<Value> dvals;
+      if (req_meta.push) dvals = detail::ToDeviceAsync(req_data.vals, dev);
+      if (req_meta.pull) {
+        // the worker's own output slice when it offered one of n * width
+        // values (written in place: no reply frame, no merge)
+        dout = server->TakeDirectOut(n * w);
+        direct = !dout.empty();
+        if (!direct) dout = SVector<Value>::OnDevice(n * w, dev);
+      }
+      stage::Scope t(req_meta.push ? "server.handle.rows.push" : "server.handle.rows.pull");
+      // returns once keys and vals are no longer read and the reply is in memory
+      device::Check(psg_table_handle(state->table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
+                    "psg_table_handle");
+    }
+    if (req_meta.pull) {
+      res.keys = req_data.keys;
+      if (!direct) res.vals = on_dev ? dout : detail::ToHost(dout);
+    }
+    server->Response(req_meta, res);
+  }
+};
+
+}  // namespace ps

@@ -46,7 +46,9 @@ EXPORTS = [
     "psg_store_handle", "psg_store_handle_async", "psg_store_wait", "psg_sort_pairs_u64", "psg_store_resolve", "psg_store_handle_slots",
     "psg_store_slots_stretch", "psg_store_handle_stretch", "psg_store_sync", "psg_store_dump",
     "psg_key_list_hash", "psg_store_push_frames", "psg_store_push_slots_frames", "psg_store_run",
-    "psg_store_run_status", "psg_store_set_key_range", "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
+    "psg_store_run_status", "psg_store_set_key_range",
+    "psg_table_create", "psg_table_destroy", "psg_table_get_info", "psg_table_clear", "psg_table_handle",
+    "psg_table_dump", "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
     "psg_comm_push_pull", "psg_comm_push_keyed", "psg_comm_pull_keyed",
     "psg_comm_bucket_plan", "psg_comm_keyed_plan", "psg_comm_sync", "psg_comm_abort",
@@ -71,6 +73,12 @@ class StoreInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("dtype", C.c_int), ("key_begin", C.c_uint64),
                 ("key_end", C.c_uint64), ("size", C.c_uint64), ("capacity", C.c_uint64),
                 ("vals", C.c_void_p), ("keys", C.c_void_p)]
+
+
+class TableInfo(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("width", C.c_uint32), ("key_begin", C.c_uint64),
+                ("key_end", C.c_uint64), ("size", C.c_uint64), ("capacity", C.c_uint64),
+                ("rows", C.c_void_p), ("keys", C.c_void_p)]
 
 
 class Segment(C.Structure):
@@ -137,6 +145,12 @@ def lib() -> C.CDLL:
                                       C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(i32)], i32),
             "psg_slice_hint": ([vp, u64, i32, u64, vp, C.POINTER(i32)], i32),
             "psg_store_set_key_range": ([vp, u64, u64], i32),
+            "psg_table_create": ([i32, C.c_uint32, u64, u64, u64, C.POINTER(vp)], i32),
+            "psg_table_destroy": ([vp], i32),
+            "psg_table_get_info": ([vp, C.POINTER(TableInfo)], i32),
+            "psg_table_clear": ([vp, vp], i32),
+            "psg_table_handle": ([vp, i32, vp, vp, vp, u64, vp], i32),
+            "psg_table_dump": ([vp, vp, vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -477,6 +491,50 @@ class Store:
     def close(self) -> None:
         if self.h.value:
             _call("psg_store_destroy", self.h)
+            self.h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- row-valued table -------------------------------------------------------------
+class Table:
+    """One server shard's row-valued table in HBM (psg_table_*): `width`
+    elements of `dtype` per key."""
+
+    def __init__(self, dtype: int, width: int, key_begin: int, key_end: int, capacity: int):
+        self.h = C.c_void_p(None)
+        _call("psg_table_create", dtype, width, key_begin, key_end, capacity, C.byref(self.h))
+        self.dtype = dtype
+        self.width = width
+        self.esize = _ESIZE[dtype]
+
+    def info(self) -> TableInfo:
+        i = TableInfo()
+        _call("psg_table_get_info", self.h, C.byref(i))
+        return i
+
+    def handle(self, flags: int, keys, vals, out, n: int, stream=None) -> None:
+        """keys: n ascending device keys; vals / out: n * width elements."""
+        _call("psg_table_handle", self.h, flags, _ptr(keys), _ptr(vals), _ptr(out), n, _s(stream))
+
+    def clear(self, stream=None) -> None:
+        _call("psg_table_clear", self.h, _s(stream))
+
+    def dump(self):
+        """(keys, rows.reshape(size, width)) in key order."""
+        i = self.info()
+        keys = np.empty(i.size, dtype=np.uint64)
+        rows = np.empty(i.size * self.width, dtype=_NP[self.dtype])
+        _call("psg_table_dump", self.h, keys.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p))
+        return keys, rows.reshape(i.size, self.width)
+
+    def close(self) -> None:
+        if self.h.value:
+            _call("psg_table_destroy", self.h)
             self.h = C.c_void_p(None)
 
     def __del__(self):
