@@ -486,6 +486,39 @@ int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* 
  * info.size * width elements.  Synchronous. */
 int psg_table_dump(psg_table* t, uint64_t* keys_host, void* rows_host);
 
+/* Give an F32 table Adam state: the moments m and v of tests/src/Adam.h:14-18,
+ * 40-41, one double each per row element, kept in HBM beside the rows; zero
+ * for every row present and for every row inserted later.  They follow their
+ * rows through inserts and growth and are dropped by psg_table_clear.  Fails
+ * with PSG_ERR_UNSUPPORTED on a non-F32 table, with PSG_ERR_INVALID on a second
+ * call, for beta1 or beta2 outside [0, 1) or epsilon < 0 — all before any
+ * device call. */
+int psg_table_set_adam(psg_table* t, double learning_rate, double beta1, double beta2,
+                       double epsilon);
+/* One gradient request: the async-mode update of tests/src/LRServer.h:171-189
+ * on the rows of a sparse key list.  For i < n, j < width:
+ *   double g = (double)(lr * grads[i*width + j]);      // f32 product, widened
+ *   if the table has Adam state (Adam.h:28-34, same operation order):
+ *     m = beta1*m + (1-beta1)*g;   v = beta2*v + ((1-beta2)*g)*g;
+ *     g = learning_rate * (m / c1) / (sqrt(v / c2) + epsilon);
+ *   row(key_i)[j] = (float)((double)row(key_i)[j] - g);
+ *   if (flags & PSG_PULL) out[i*width + j] = row(key_i)[j];   // post-update
+ * with c1 = 1 - pow(beta1, iteration+1), c2 = 1 - pow(beta2, iteration+1),
+ * evaluated once on the host.  `iteration` (>= 0) is the caller's one global
+ * step count, as in the reference: there is no per-row count.  flags: PSG_PUSH
+ * or PSG_PUSH | PSG_PULL (else PSG_ERR_INVALID).  F32 tables only
+ * (PSG_ERR_UNSUPPORTED).  Keys, validation and return as psg_table_handle: keys
+ * strictly ascending, every key checked before the first write, a rejected
+ * request (PSG_ERR_INVALID / PSG_ERR_RANGE) leaves rows and moments bit for bit
+ * unchanged; an absent key is inserted with a zero row and zero moments, then
+ * updated.  n == 0 is a no-op. */
+int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float* grads,
+                     float* out, uint64_t n, float lr, int iteration, psg_stream stream);
+/* The Adam moments in key order, info.size * width doubles each (whatever the
+ * layout in HBM).  Fails with PSG_ERR_INVALID on a table without Adam state.
+ * Synchronous. */
+int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host);
+
 /* ======================================================================== */
 /* Worker side: key-range slicing and pull merge                              */
 /* ======================================================================== */

@@ -24,8 +24,20 @@
 //                    elements, so consecutive slots read and write consecutive
 //                    memory; one writer per row (keys are unique): no atomics.
 // Algorithmic bytes per f32 key of a Push: key 8 + slot 4 + 4 + 12 * width.
+//
+// The optimizer update (psg_table_update) is the same two passes with
+// k_rows_update in place of k_rows_apply: the async-mode LRServer handle
+// (tests/src/LRServer.h:179-189) with SGD or Adam (tests/src/Adam.h:28-34) on
+// the rows a gradient Push names.  The Adam moments are f64 rows beside the
+// value rows, one array M[S x 2 width] in slot order: a row's m values, then
+// its v values, so one row's state is one contiguous run and an insert moves
+// it with one k_rows_move of `width` 16-B units through the same slot map.
+// Where width is a multiple of 4 each half is kept in the lane order of the
+// 16-B path (mom_col below).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "psg_internal.h"
 
@@ -42,6 +54,11 @@ struct psg_table {
   uint64_t slots_cap;
   int* flags;       // device view of flags_host
   int* flags_host;  // pinned host int[kNFlags], raised by k_rows_resolve
+  // Adam state (psg_table_set_adam): the parameters of Adam.h:14-18 and the
+  // moments, capacity * 2 * width doubles in slot order (null while capacity == 0)
+  int adam;
+  double alr, beta1, beta2, eps;
+  double* mom;
 };
 
 namespace psg {
@@ -274,6 +291,119 @@ __global__ __launch_bounds__(256) void k_rows_apply(typename Unit<DT, VEC>::U* _
   }
 }
 
+// ---- the optimizer update ----------------------------------------------------
+// Where in its half (m or v) of a moment row the moment of column j lives.
+// width % 4 == 0: the unit of four columns 4u..4u+3 keeps the pair (4u, 4u+1)
+// at doubles 2u, 2u+1 and the pair (4u+2, 4u+3) at width/2 + 2u, so a lane of
+// the 16-B path, which owns one unit, loads each pair as 16 B and consecutive
+// lanes load consecutive memory: four runs of 16 B a lane per wave instruction
+// instead of two 32-B-strided ones that each touch half of every line (what
+// psg_lr.hip's QUAD layout does for the dense weights).  Other widths: column
+// order.
+__host__ __device__ inline uint32_t mom_col(uint32_t j, uint32_t width) {
+  if (width % 4) return j;
+  return ((j >> 1) & 1) * (width / 2) + 2 * (j >> 2) + (j & 1);
+}
+
+struct AdamArgs {
+  double alr, b1, b2, eps, c1, c2;
+};
+
+// Pass 2 of psg_table_update.  Request row i (slot slots[i]) for i < n; every
+// slot is present.  Per element (LRServer.h:182-189, Adam.h:28-34):
+//   g = (double)(lr * grad); Adam: m, v updated, g = alr * (m / c1) / (sqrt(v / c2) + eps);
+//   row = (float)((double)row - g); the Pull's reply is the updated row.
+// VEC: a unit is four columns (16 B of gradient, 16 B of row, four 16-B moment
+// pairs); else one column.  Every load of a step is issued before its
+// arithmetic; SGD keeps kUnroll units in flight, Adam two (24 data registers a
+// unit and the f64 divide and square root on top).
+template <bool ADAM, int OP, bool VEC>
+__global__ __launch_bounds__(256) void k_rows_update(float* __restrict__ R, double* __restrict__ M,
+                                                     const uint32_t* __restrict__ slots,
+                                                     const float* __restrict__ grads, float* __restrict__ out,
+                                                     uint64_t n, uint32_t upr, uint32_t rpt, uint32_t width, float lr,
+                                                     AdamArgs a) {
+  constexpr int E = VEC ? 4 : 1;
+  constexpr int UN = ADAM ? 2 : kUnroll;
+  const uint32_t half = width / 2;
+  const uint64_t ntiles = (n + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t i0 = t * rpt;
+    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += UN * kBlock) {
+      uint64_t so[UN], ro[UN], mo[UN];  // offsets of the unit: row (floats), request (floats), m (doubles)
+      bool ok[UN];
+      float s[UN][E], g[UN][E];
+      double q[UN][2 * E];  // m of the unit's columns, then v
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t i = i0 + w.r;
+          const uint64_t slot = slots[i];
+          so[k] = (slot * upr + w.c) * E;
+          ro[k] = (i * upr + w.c) * E;
+          if constexpr (ADAM) mo[k] = slot * 2 * width + (VEC ? 2 * w.c : mom_col(w.c, width));
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        if (!ok[k]) continue;
+        if constexpr (VEC) {
+          const f32x4 sv = *reinterpret_cast<const f32x4*>(R + so[k]);
+          const f32x4 gv = *reinterpret_cast<const f32x4*>(grads + ro[k]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s[k][e] = sv[e], g[k][e] = gv[e];
+          if constexpr (ADAM) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const f64x2 p = *reinterpret_cast<const f64x2*>(M + mo[k] + (uint64_t)r * half);
+              q[k][2 * r] = p[0], q[k][2 * r + 1] = p[1];
+            }
+          }
+        } else {
+          s[k][0] = R[so[k]];
+          g[k][0] = grads[ro[k]];
+          if constexpr (ADAM) q[k][0] = M[mo[k]], q[k][1] = M[mo[k] + width];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        if (!ok[k]) continue;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          double gr = (double)(lr * g[k][e]);
+          if constexpr (ADAM) {
+            const double mi = a.b1 * q[k][e] + (1.0 - a.b1) * gr;
+            const double vi = a.b2 * q[k][E + e] + (1.0 - a.b2) * gr * gr;
+            q[k][e] = mi;
+            q[k][E + e] = vi;
+            gr = a.alr * (mi / a.c1) / (sqrt(vi / a.c2) + a.eps);
+          }
+          s[k][e] = (float)((double)s[k][e] - gr);
+        }
+        if constexpr (VEC) {
+          if constexpr (ADAM) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              *reinterpret_cast<f64x2*>(M + mo[k] + (uint64_t)r * half) = f64x2{q[k][2 * r], q[k][2 * r + 1]};
+          }
+          const f32x4 sv = {s[k][0], s[k][1], s[k][2], s[k][3]};
+          *reinterpret_cast<f32x4*>(R + so[k]) = sv;
+          if constexpr ((OP & PSG_PULL) != 0) *reinterpret_cast<f32x4*>(out + ro[k]) = sv;
+        } else {
+          if constexpr (ADAM) M[mo[k]] = q[k][0], M[mo[k] + width] = q[k][1];
+          R[so[k]] = s[k][0];
+          if constexpr ((OP & PSG_PULL) != 0) out[ro[k]] = s[k][0];
+        }
+      }
+    }
+  }
+}
+
 unsigned grid_for(uint64_t blocks) {
   const uint64_t cap = (uint64_t)max_stream_blocks();
   if (blocks > cap) blocks = cap;
@@ -319,6 +449,36 @@ int apply(psg_table* t, int op, const void* vals, void* out, uint64_t n, hipStre
   }
 }
 
+template <bool ADAM, bool VEC>
+int launch_update(psg_table* t, int op, const float* grads, float* out, uint64_t n, float lr, const AdamArgs& a,
+                  hipStream_t st) {
+  const uint32_t upr = VEC ? t->width / 4 : t->width;
+  const uint32_t rpt = rows_per_tile(upr);
+  const unsigned g = grid_for((n + rpt - 1) / rpt);
+  float* R = (float*)t->rows;
+  if (op == PSG_PUSH)
+    k_rows_update<ADAM, PSG_PUSH, VEC><<<g, kBlock, 0, st>>>(R, t->mom, t->slots, grads, out, n, upr, rpt, t->width, lr, a);
+  else
+    k_rows_update<ADAM, PSG_PUSH | PSG_PULL, VEC>
+        <<<g, kBlock, 0, st>>>(R, t->mom, t->slots, grads, out, n, upr, rpt, t->width, lr, a);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+int update(psg_table* t, int op, const float* grads, float* out, uint64_t n, float lr, int iteration, hipStream_t st) {
+  // 16-B vectors when every row, here and in the request, starts on 16 B
+  const bool vec = t->width % 4 == 0 && aligned16(grads) && (!(op & PSG_PULL) || aligned16(out));
+  AdamArgs a = {};
+  if (!t->adam) return vec ? launch_update<false, true>(t, op, grads, out, n, lr, a, st)
+                           : launch_update<false, false>(t, op, grads, out, n, lr, a, st);
+  // the two bias corrections of Adam.h:31-32, with the host libm pow the
+  // reference calls (as psg_lr.hip)
+  a = {t->alr, t->beta1, t->beta2, t->eps, 1 - std::pow(t->beta1, iteration + 1),
+       1 - std::pow(t->beta2, iteration + 1)};
+  return vec ? launch_update<true, true>(t, op, grads, out, n, lr, a, st)
+             : launch_update<true, false>(t, op, grads, out, n, lr, a, st);
+}
+
 template <typename U>
 int launch_move(const void* src, void* dst, const uint32_t* to, uint64_t nrows, uint32_t upr, hipStream_t st) {
   const uint32_t rpt = rows_per_tile(upr);
@@ -334,6 +494,8 @@ int move_rows(const psg_table* t, const void* src, void* dst, const uint32_t* to
   if (rb % 4 == 0) return launch_move<uint32_t>(src, dst, to, nrows, rb / 4, st);
   return launch_move<uint16_t>(src, dst, to, nrows, rb / 2, st);
 }
+
+inline uint64_t mom_row_bytes(const psg_table* t) { return (uint64_t)t->width * 2 * sizeof(double); }
 
 int ensure_slots(psg_table* t, uint64_t n) {
   if (t->slots_cap >= n) return PSG_OK;
@@ -388,21 +550,49 @@ int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) 
   k_rows_compact_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(q, t->slots, n, (const uint32_t*)counts.p,
                                                               (uint64_t*)miss.p);
   PSG_HIP(hipGetLastError());
-  DevBuf K2, R2;
+  DevBuf K2, R2, M2;
   PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
   PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
+  if (t->adam) PSG_HIP(hipMalloc(&M2.p, cap * mom_row_bytes(t)));
   k_rows_merge_keys<<<grid_for((S + m + kBlock - 1) / kBlock), kBlock, 0, st>>>(
       t->keys, S, (const uint64_t*)miss.p, m, (uint64_t*)K2.p, (uint32_t*)old_to.p, (uint32_t*)new_to.p);
   PSG_HIP(hipGetLastError());
   if (S) PSG_TRY(move_rows(t, t->rows, R2.p, (const uint32_t*)old_to.p, S, st));
   PSG_TRY(move_rows(t, nullptr, R2.p, (const uint32_t*)new_to.p, m, st));
+  if (t->adam) {  // the moment rows go where their value rows went: 2 * width doubles = width 16-B units
+    if (S) PSG_TRY(launch_move<u32x4>(t->mom, M2.p, (const uint32_t*)old_to.p, S, t->width, st));
+    PSG_TRY(launch_move<u32x4>(nullptr, M2.p, (const uint32_t*)new_to.p, m, t->width, st));
+  }
   PSG_HIP(hipStreamSynchronize(st));
   void* old_keys = t->keys;  // the old arrays are freed with K2 / R2
   t->keys = (uint64_t*)K2.p;
   K2.p = old_keys;
   std::swap(R2.p, t->rows);
+  if (t->adam) {
+    void* old_mom = t->mom;
+    t->mom = (double*)M2.p;
+    M2.p = old_mom;
+  }
   t->size = S + m;
   t->capacity = cap;
+  return PSG_OK;
+}
+
+// Both passes' front half: resolve q into t->slots, reject a bad list before
+// anything is written, insert the absent keys.
+int resolve_request(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
+  PSG_TRY(ensure_slots(t, n));
+  PSG_TRY(resolve(t, keys, n, st));
+  const int* f = t->flags_host;
+  PSG_REQUIRE(!f[R_UNSORTED], PSG_ERR_INVALID,
+              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
+  PSG_REQUIRE(!f[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
+              (unsigned long long)t->key_begin, (unsigned long long)t->key_end);
+  if (f[R_MISSING]) {
+    PSG_TRY(insert_missing(t, keys, n, st));
+    PSG_TRY(resolve(t, keys, n, st));
+    PSG_REQUIRE(!t->flags_host[R_MISSING], PSG_ERR_HIP, "psg_table: a key is absent after its insert");
+  }
   return PSG_OK;
 }
 
@@ -455,6 +645,7 @@ int psg_table_destroy(psg_table* t) {
   if (t->rows) (void)hipFree(t->rows);
   if (t->keys) (void)hipFree(t->keys);
   if (t->slots) (void)hipFree(t->slots);
+  if (t->mom) (void)hipFree(t->mom);
   if (t->flags_host) (void)hipHostFree(t->flags_host);
   delete t;
   return PSG_OK;
@@ -490,18 +681,7 @@ int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* 
   PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
   PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_handle: more than 2^32-2 keys in one request");
   hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(ensure_slots(t, n));
-  PSG_TRY(resolve(t, keys, n, st));
-  const int* f = t->flags_host;
-  PSG_REQUIRE(!f[R_UNSORTED], PSG_ERR_INVALID,
-              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
-  PSG_REQUIRE(!f[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
-              (unsigned long long)t->key_begin, (unsigned long long)t->key_end);
-  if (f[R_MISSING]) {
-    PSG_TRY(insert_missing(t, keys, n, st));
-    PSG_TRY(resolve(t, keys, n, st));
-    PSG_REQUIRE(!t->flags_host[R_MISSING], PSG_ERR_HIP, "psg_table_handle: a key is absent after its insert");
-  }
+  PSG_TRY(resolve_request(t, keys, n, st));
   PSG_TRY(apply(t, flags, vals, out, n, st));
   // complete on return: keys and vals no longer read, a Pull's reply in memory
   PSG_HIP(hipStreamSynchronize(st));
@@ -514,6 +694,71 @@ int psg_table_dump(psg_table* t, uint64_t* keys_host, void* rows_host) {
   if (t->size == 0) return PSG_OK;
   PSG_HIP(hipMemcpy(rows_host, t->rows, t->size * (uint64_t)t->width * t->esize, hipMemcpyDeviceToHost));
   if (keys_host) PSG_HIP(hipMemcpy(keys_host, t->keys, t->size * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PSG_OK;
+}
+
+int psg_table_set_adam(psg_table* t, double learning_rate, double beta1, double beta2, double epsilon) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_set_adam: null table");
+  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "psg_table_set_adam: the update is built for F32 tables");
+  PSG_REQUIRE(!t->adam, PSG_ERR_INVALID, "psg_table_set_adam: the table already has Adam state");
+  PSG_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1, PSG_ERR_INVALID,
+              "psg_table_set_adam: beta1 %g / beta2 %g outside [0, 1)", beta1, beta2);
+  PSG_REQUIRE(epsilon >= 0, PSG_ERR_INVALID, "psg_table_set_adam: epsilon %g below 0", epsilon);
+  if (t->capacity) {
+    double* mom = nullptr;
+    PSG_HIP(hipMalloc((void**)&mom, t->capacity * mom_row_bytes(t)));
+    // null-stream memset, waited for: done before the caller's streams use the moments
+    hipError_t e = t->size ? hipMemset(mom, 0, t->size * mom_row_bytes(t)) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+      (void)hipFree(mom);
+      return hip_fail(e, "psg_table_set_adam", __FILE__, __LINE__);
+    }
+    t->mom = mom;
+  }
+  t->adam = 1;
+  t->alr = learning_rate;
+  t->beta1 = beta1;
+  t->beta2 = beta2;
+  t->eps = epsilon;
+  return PSG_OK;
+}
+
+int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float* grads, float* out, uint64_t n,
+                     float lr, int iteration, psg_stream stream) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_update: null table");
+  PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
+              "psg_table_update: flags %d are neither PUSH nor PUSH|PULL", flags);
+  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "psg_table_update: iteration %d below 0", iteration);
+  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "psg_table_update: the update is built for F32 tables");
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_update: null keys");
+  PSG_REQUIRE(grads, PSG_ERR_INVALID, "psg_table_update: null grads");
+  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_update: more than 2^32-2 keys in one request");
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(resolve_request(t, keys, n, st));
+  PSG_TRY(update(t, flags, grads, out, n, lr, iteration, st));
+  // complete on return, as psg_table_handle
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_dump_moments: null table");
+  PSG_REQUIRE(t->adam, PSG_ERR_INVALID, "psg_table_dump_moments: the table has no Adam state");
+  if (t->size == 0) return PSG_OK;
+  PSG_REQUIRE(m_host && v_host, PSG_ERR_INVALID, "psg_table_dump_moments: null argument");
+  PSG_HIP(hipDeviceSynchronize());
+  const uint64_t W = t->width;
+  std::vector<double> raw(t->size * 2 * W);
+  PSG_HIP(hipMemcpy(raw.data(), t->mom, raw.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (uint64_t r = 0; r < t->size; ++r)
+    for (uint32_t j = 0; j < W; ++j) {
+      const uint32_t c = mom_col(j, t->width);
+      m_host[r * W + j] = raw[r * 2 * W + c];
+      v_host[r * W + j] = raw[r * 2 * W + W + c];
+    }
   return PSG_OK;
 }
 

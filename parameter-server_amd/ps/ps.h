@@ -9,6 +9,7 @@
 #include "ps/base.h"
 #include "ps/kv_app.h"
 #include "ps/row_handle.h"
+#include "ps/row_opt_handle.h"
 #include "ps/simple_app.h"
 
 namespace ps {

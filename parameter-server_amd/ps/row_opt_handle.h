@@ -1,0 +1,113 @@
+// ps/row_opt_handle.h — a server handle that trains rows of `width` floats per
+// key in HBM: the async-mode LR server's handle on a row table.
+//
+// Reference: lr::LRServer::RequestHandle in async mode (tests/src/LRServer.h:
+// 179-206) with Adam (tests/src/Adam.h:28-34), applied to the rows a gradient
+// Push names instead of one dense weight vector:
+//
+//   Push, cmd 0 or 1:  width gradients per key, applied at once with the
+//                      current iteration (psg_table_update: SGD, or Adam with
+//                      its moments beside the rows); a PushPull answers with
+//                      the updated rows.  After a Push with cmd == 1 from
+//                      worker 0 is applied the iteration goes up by one
+//                      (LRServer.h:193-195).
+//   Push, cmd 2:       kAccumulate — row(key_i)[j] += vals[i * width + j]
+//                      (psg_table_handle), how a worker seeds rows; the
+//                      moments are untouched.
+//   Pull:              res.vals[i * width + j] = row(key_i)[j].
+//
+// The rows live in a psg_table over [0, kMaxKey), created on the first request;
+// an absent key starts from a zero row and zero moments.  Adam gets
+// ((double)learning_rate, 0.9, 0.999, 1e-8), as LRServer.h:83-84 constructs it.
+// The iteration is the server's one counter, as in the reference: there is no
+// per-row step count.  Keys must be strictly ascending (KVApp.h:23).  Register
+// with KVServer::SetDeviceRequestHandle; host frames are staged into HBM.
+#pragma once
+#include <memory>
+
+#include "ps/kv_app.h"
+
+namespace ps {
+
+struct KVServerRowOptHandle {
+  static constexpr int kAccumulate = 2;  // cmd of a Push that adds to the rows instead of training them
+
+  struct State {
+    psg_table* table = nullptr;
+    uint32_t width = 0;
+    float lr = 0.01f;
+    bool use_adam = false;
+    int iteration = 0;
+    ~State() {
+      if (table) psg_table_destroy(table);
+    }
+  };
+  std::shared_ptr<State> state = std::make_shared<State>();
+
+  KVServerRowOptHandle(uint32_t width, float learning_rate, bool use_adam, int start_iteration = 0) {
+    CHECK(width >= 1 && width <= 4096) << "KVServerRowOptHandle: width " << width << " outside [1, 4096]";
+    CHECK_GE(start_iteration, 0);
+    state->width = width;
+    state->lr = learning_rate;
+    state->use_adam = use_adam;
+    state->iteration = start_iteration;
+  }
+
+  void operator()(const KVMeta& req_meta, const KVPairs<float>& req_data, KVServer<float>* server) {
+    State& st = *state;
+    const size_t n = req_data.keys.size();
+    const size_t w = st.width;
+    KVPairs<float> res;
+    const int dev = PostOffice::Get()->device();
+    CHECK_GE(dev, 0) << "KVServerRowOptHandle: the table lives in HBM and this node has no GPU";
+    CHECK(req_data.lens.empty()) << "KVServerRowOptHandle: rows have one fixed width, lens are not supported";
+    if (!st.table) {
+      device::Check(psg_table_create(PSG_F32, st.width, 0, kMaxKey, 0, &st.table), "psg_table_create");
+      if (st.use_adam)
+        device::Check(psg_table_set_adam(st.table, (double)st.lr, 0.9, 0.999, 1e-8), "psg_table_set_adam");
+    }
+    const bool on_dev = req_data.keys.on_device();
+    const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
+    const bool accumulate = req_meta.push && req_meta.cmd == kAccumulate;
+    if (req_meta.push) {
+      CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
+      CHECK(req_meta.cmd >= 0 && req_meta.cmd <= kAccumulate) << "KVServerRowOptHandle: unknown Push cmd " << req_meta.cmd;
+    }
+    SVector<float> dout;
+    bool direct = false;
+    if (n && flags) {
+      psg_stream s = device::ThreadStream();
+      SVector<Key> dkeys = detail::ToDeviceAsync(req_data.keys, dev);
+      SVector<float> dvals;
+      if (req_meta.push) dvals = detail::ToDeviceAsync(req_data.vals, dev);
+      if (req_meta.pull) {
+        // the worker's own output slice when it offered one of n * width
+        // values (written in place: no reply frame, no merge)
+        dout = server->TakeDirectOut(n * w);
+        direct = !dout.empty();
+        if (!direct) dout = SVector<float>::OnDevice(n * w, dev);
+      }
+      stage::Scope t(!req_meta.push ? "server.handle.rows.pull"
+                                    : accumulate ? "server.handle.rows.push" : "server.handle.rows.update");
+      // both return once keys and vals are no longer read and the reply is in memory
+      if (req_meta.push && !accumulate)
+        device::Check(psg_table_update(st.table, flags, dkeys.data(), dvals.data(), dout.data(), n, st.lr,
+                                       st.iteration, s),
+                      "psg_table_update");
+      else
+        device::Check(psg_table_handle(st.table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
+                      "psg_table_handle");
+    }
+    // LRServer.h:193-195: worker 0's Push with cmd 1 ends an iteration
+    if (req_meta.push && req_meta.cmd == 1 && req_meta.sender == PostOffice::WorkerRankToID(0)) ++st.iteration;
+    if (req_meta.pull) {
+      res.keys = req_data.keys;
+      if (!direct) res.vals = on_dev ? dout : detail::ToHost(dout);
+    }
+    server->Response(req_meta, res);
+  }
+
+  int iteration() const { return state->iteration; }
+};
+
+}  // namespace ps

@@ -48,7 +48,8 @@ EXPORTS = [
     "psg_key_list_hash", "psg_store_push_frames", "psg_store_push_slots_frames", "psg_store_run",
     "psg_store_run_status", "psg_store_set_key_range",
     "psg_table_create", "psg_table_destroy", "psg_table_get_info", "psg_table_clear", "psg_table_handle",
-    "psg_table_dump", "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
+    "psg_table_dump", "psg_table_set_adam", "psg_table_update", "psg_table_dump_moments",
+    "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
     "psg_comm_push_pull", "psg_comm_push_keyed", "psg_comm_pull_keyed",
     "psg_comm_bucket_plan", "psg_comm_keyed_plan", "psg_comm_sync", "psg_comm_abort",
@@ -151,6 +152,9 @@ def lib() -> C.CDLL:
             "psg_table_clear": ([vp, vp], i32),
             "psg_table_handle": ([vp, i32, vp, vp, vp, u64, vp], i32),
             "psg_table_dump": ([vp, vp, vp], i32),
+            "psg_table_set_adam": ([vp, f64, f64, f64, f64], i32),
+            "psg_table_update": ([vp, i32, vp, vp, vp, u64, f32, i32, vp], i32),
+            "psg_table_dump_moments": ([vp, vp, vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -531,6 +535,23 @@ class Table:
         rows = np.empty(i.size * self.width, dtype=_NP[self.dtype])
         _call("psg_table_dump", self.h, keys.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p))
         return keys, rows.reshape(i.size, self.width)
+
+    def set_adam(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
+        """Adam moments (f64, zero) beside every row; an update then runs Adam.h:28-34."""
+        _call("psg_table_set_adam", self.h, lr, beta1, beta2, eps)
+
+    def update(self, flags: int, keys, grads, out, n: int, lr: float, iteration: int, stream=None) -> None:
+        """One gradient request (psg_table_update): SGD, or Adam after set_adam, on
+        the rows of n ascending device keys; grads / out: n * width floats."""
+        _call("psg_table_update", self.h, flags, _ptr(keys), _ptr(grads), _ptr(out), n, lr, iteration, _s(stream))
+
+    def dump_moments(self):
+        """(m, v), each shaped (size, width), in key order."""
+        i = self.info()
+        m = np.empty(i.size * self.width, dtype=np.float64)
+        v = np.empty(i.size * self.width, dtype=np.float64)
+        _call("psg_table_dump_moments", self.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p))
+        return m.reshape(i.size, self.width), v.reshape(i.size, self.width)
 
     def close(self) -> None:
         if self.h.value:
