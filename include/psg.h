@@ -475,12 +475,27 @@ int psg_table_clear(psg_table* t, psg_stream stream);
  * is inserted with a zero row, on a Push and on a Pull (operator[]).  Keys out
  * of order or repeated fail the request with PSG_ERR_INVALID, a key outside
  * the range with PSG_ERR_RANGE; every key is checked before the first write,
- * so a request that fails leaves the table bit for bit unchanged (the
- * order-preserving path psg_store_handle has for such lists is not built for
- * rows).  Returns as psg_store_handle does: keys and vals are no longer read
+ * so a request that fails leaves the table bit for bit unchanged (such lists
+ * are served by psg_table_handle_any below).  Returns as psg_store_handle does: keys and vals are no longer read
  * and a Pull's reply is in memory.  n == 0 is a no-op. */
 int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* vals,
                      void* out, uint64_t n, psg_stream stream);
+/* psg_table_handle for a key list in any order and with repeats, as the
+ * reference's loop serves it (src/ps/KVApp.h:446-454 never looks at the order):
+ * the result — rows and the Pull's reply, bit for bit — is that of the n
+ * one-key requests psg_table_handle(t, flags, keys + i, vals + i*width,
+ * out + i*width, 1, stream) for i = 0 .. n-1.  Every occurrence of a key is
+ * applied in arrival order and rounded on its own; a PushPull answers each
+ * occurrence with the running row after it, a Pull answers every occurrence
+ * with the row; an absent key is inserted once, with a zero row, however often
+ * it is named.  A strictly ascending list is served exactly as psg_table_handle
+ * serves it (the same kernels); any other list is sorted stably by key on the
+ * device and each row is walked over its occurrences by one writer.  Arguments
+ * are checked as psg_table_handle checks them; a key outside the range fails
+ * the request with PSG_ERR_RANGE before anything is written.  The caller's
+ * keys are never written.  Returns as psg_table_handle.  n == 0 is a no-op. */
+int psg_table_handle_any(psg_table* t, int flags, const uint64_t* keys, const void* vals,
+                         void* out, uint64_t n, psg_stream stream);
 /* Copy the table (src/ps/KVApp.h:446-454's store, k values per key, KVApp.h:515-574)
  * to host memory in key order: info.size keys (keys_host may be NULL) and
  * info.size * width elements.  Synchronous. */
@@ -514,6 +529,17 @@ int psg_table_set_adam(psg_table* t, double learning_rate, double beta1, double 
  * updated.  n == 0 is a no-op. */
 int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float* grads,
                      float* out, uint64_t n, float lr, int iteration, psg_stream stream);
+/* psg_table_update for a key list in any order and with repeats: rows, moments
+ * and the reply are, bit for bit, those of the n one-key requests
+ * psg_table_update(t, flags, keys + i, grads + i*width, out + i*width, 1, lr,
+ * iteration, stream) for i = 0 .. n-1.  Every occurrence uses the request's one
+ * `iteration` (c1 and c2 are evaluated once); the moments advance once per
+ * occurrence; an absent key starts from a zero row and zero moments and is
+ * inserted once.  Checks, the PSG_ERR_RANGE failure that writes nothing, the
+ * strictly ascending fast path and the return are those of
+ * psg_table_handle_any and psg_table_update. */
+int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const float* grads,
+                         float* out, uint64_t n, float lr, int iteration, psg_stream stream);
 /* The Adam moments in key order, info.size * width doubles each (whatever the
  * layout in HBM).  Fails with PSG_ERR_INVALID on a table without Adam state.
  * Synchronous. */

@@ -59,6 +59,10 @@ struct psg_table {
   int adam;
   double alr, beta1, beta2, eps;
   double* mom;
+  // scratch of the order-preserving requests (psg_table_*_any): the sort's
+  // buffers, perm, U and seg carved from one block grown on demand
+  void* any_buf;
+  uint64_t any_bytes;
 };
 
 namespace psg {
@@ -404,6 +408,200 @@ __global__ __launch_bounds__(256) void k_rows_update(float* __restrict__ R, doub
   }
 }
 
+// ---- the order-preserving request (psg_table_*_any) ---------------------------
+// The list is sorted stably by key with its positions (radix_sort_u64, iota):
+// sorted[n] and perm[n].  The heads of the runs of equal keys give the strictly
+// ascending unique list U[m] and seg[m + 1], the bounds of each key's
+// occurrences in perm — in arrival order, the sort being stable.  Same tiles as
+// the missing-key compaction above: 1024 positions a block, 4 a lane.
+__device__ __forceinline__ bool seg_head(const uint64_t* __restrict__ sorted, uint64_t i) {
+  return i == 0 || sorted[i - 1] != sorted[i];
+}
+
+__global__ __launch_bounds__(256) void k_rows_tile_heads(const uint64_t* __restrict__ sorted, uint64_t n,
+                                                         uint32_t* __restrict__ counts) {
+  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kRowTile / kBlock; ++k)
+    if (i0 + k < n && seg_head(sorted, i0 + k)) c++;
+  uint32_t tot;
+  block_excl_scan(c, &tot);
+  if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+}
+
+// offs: the scanned tile counts, offs[ntiles] = m
+__global__ __launch_bounds__(256) void k_rows_compact_heads(const uint64_t* __restrict__ sorted, uint64_t n,
+                                                            const uint32_t* __restrict__ offs, uint64_t ntiles,
+                                                            uint64_t* __restrict__ U, uint32_t* __restrict__ seg) {
+  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kRowTile / kBlock; ++k)
+    if (i0 + k < n && seg_head(sorted, i0 + k)) c++;
+  uint32_t tot;
+  uint32_t pos = offs[blockIdx.x] + block_excl_scan(c, &tot);
+#pragma unroll
+  for (int k = 0; k < kRowTile / kBlock; ++k)
+    if (i0 + k < n && seg_head(sorted, i0 + k)) {
+      U[pos] = sorted[i0 + k];
+      seg[pos++] = (uint32_t)(i0 + k);
+    }
+  if (blockIdx.x == 0 && threadIdx.x == 0) seg[offs[ntiles]] = (uint32_t)n;
+}
+
+// Pass 2 of psg_table_handle_any.  Unique row u (slot slots[u]) for u < m; its
+// occurrences are request rows perm[seg[u] .. seg[u + 1]), in arrival order.
+// The lanes walk the unique rows as k_rows_apply walks request rows; a lane
+// loads its unit of the row once, runs over the occurrences (add, reply with
+// the running row) and stores the unit once: one writer per row, no atomics.
+// The loop is a chain perm -> vals -> add; the position two ahead and the
+// values one ahead are loaded before the current add.
+template <int DT, int OP, bool VEC>
+__global__ __launch_bounds__(256) void k_rows_apply_seg(typename Unit<DT, VEC>::U* __restrict__ R,
+                                                        const uint32_t* __restrict__ slots,
+                                                        const uint32_t* __restrict__ seg,
+                                                        const uint32_t* __restrict__ perm,
+                                                        const typename Unit<DT, VEC>::U* __restrict__ vals,
+                                                        typename Unit<DT, VEC>::U* __restrict__ out, uint64_t m,
+                                                        uint32_t upr, uint32_t rpt) {
+  using UT = Unit<DT, VEC>;
+  using U = typename UT::U;
+  const uint64_t ntiles = (m + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t u0 = t * rpt;
+    const uint32_t nr = (uint32_t)(m - u0 < rpt ? m - u0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
+      const uint64_t u = u0 + w.r;
+      const uint64_t so = (uint64_t)slots[u] * upr + w.c;
+      uint32_t p = seg[u];
+      const uint32_t pe = seg[u + 1];  // > p: every unique key has an occurrence
+      U s = R[so];
+      uint32_t i0 = perm[p];
+      uint32_t i1 = p + 1 < pe ? perm[p + 1] : 0;
+      U v = {};
+      if constexpr ((OP & PSG_PUSH) != 0) v = vals[(uint64_t)i0 * upr + w.c];
+      for (; p < pe; ++p) {
+        const uint32_t i2 = p + 2 < pe ? perm[p + 2] : 0;
+        U vn = v;
+        if constexpr ((OP & PSG_PUSH) != 0) {
+          if (p + 1 < pe) vn = vals[(uint64_t)i1 * upr + w.c];
+          s = UT::add(s, v);
+        }
+        if constexpr ((OP & PSG_PULL) != 0) out[(uint64_t)i0 * upr + w.c] = s;
+        i0 = i1, i1 = i2, v = vn;
+      }
+      if constexpr ((OP & PSG_PUSH) != 0) R[so] = s;
+    }
+  }
+}
+
+// Pass 2 of psg_table_update_any: k_rows_update's arithmetic, expression for
+// expression, on the occurrences of each unique row in arrival order.  A lane
+// keeps its unit of the row and its moment pairs (the table's mom_col layout)
+// in registers over the segment and stores them once; the next occurrence's
+// gradients are loaded before the current one's arithmetic.
+template <bool ADAM, int OP, bool VEC>
+__global__ __launch_bounds__(256) void k_rows_update_seg(float* __restrict__ R, double* __restrict__ M,
+                                                         const uint32_t* __restrict__ slots,
+                                                         const uint32_t* __restrict__ seg,
+                                                         const uint32_t* __restrict__ perm,
+                                                         const float* __restrict__ grads, float* __restrict__ out,
+                                                         uint64_t m, uint32_t upr, uint32_t rpt, uint32_t width,
+                                                         float lr, AdamArgs a) {
+  constexpr int E = VEC ? 4 : 1;
+  const uint32_t half = width / 2;
+  const uint64_t ntiles = (m + rpt - 1) / rpt;
+  auto load_g = [&](float (&g)[E], uint32_t i, uint32_t c) {
+    const uint64_t ro = ((uint64_t)i * upr + c) * E;
+    if constexpr (VEC) {
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(grads + ro);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = gv[e];
+    } else {
+      g[0] = grads[ro];
+    }
+  };
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t u0 = t * rpt;
+    const uint32_t nr = (uint32_t)(m - u0 < rpt ? m - u0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += kBlock, w.next()) {
+      const uint64_t u = u0 + w.r;
+      const uint64_t slot = slots[u];
+      const uint64_t so = (slot * upr + w.c) * E;
+      const uint64_t mo = slot * 2 * width + (VEC ? 2 * w.c : mom_col(w.c, width));
+      uint32_t p = seg[u];
+      const uint32_t pe = seg[u + 1];  // > p
+      float s[E], g[E], gn[E];
+      double q[2 * E];  // m of the unit's columns, then v
+      if constexpr (VEC) {
+        const f32x4 sv = *reinterpret_cast<const f32x4*>(R + so);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] = sv[e];
+        if constexpr (ADAM) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const f64x2 pr = *reinterpret_cast<const f64x2*>(M + mo + (uint64_t)r * half);
+            q[2 * r] = pr[0], q[2 * r + 1] = pr[1];
+          }
+        }
+      } else {
+        s[0] = R[so];
+        if constexpr (ADAM) q[0] = M[mo], q[1] = M[mo + width];
+      }
+      uint32_t i0 = perm[p];
+      uint32_t i1 = p + 1 < pe ? perm[p + 1] : 0;
+      load_g(g, i0, w.c);
+      for (; p < pe; ++p) {
+        const uint32_t i2 = p + 2 < pe ? perm[p + 2] : 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) gn[e] = g[e];
+        if (p + 1 < pe) load_g(gn, i1, w.c);
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          double gr = (double)(lr * g[e]);
+          if constexpr (ADAM) {
+            const double mi = a.b1 * q[e] + (1.0 - a.b1) * gr;
+            const double vi = a.b2 * q[E + e] + (1.0 - a.b2) * gr * gr;
+            q[e] = mi;
+            q[E + e] = vi;
+            gr = a.alr * (mi / a.c1) / (sqrt(vi / a.c2) + a.eps);
+          }
+          s[e] = (float)((double)s[e] - gr);
+        }
+        if constexpr ((OP & PSG_PULL) != 0) {
+          const uint64_t ro = ((uint64_t)i0 * upr + w.c) * E;
+          if constexpr (VEC) {
+            const f32x4 sv = {s[0], s[1], s[2], s[3]};
+            *reinterpret_cast<f32x4*>(out + ro) = sv;
+          } else {
+            out[ro] = s[0];
+          }
+        }
+        i0 = i1, i1 = i2;
+#pragma unroll
+        for (int e = 0; e < E; ++e) g[e] = gn[e];
+      }
+      if constexpr (VEC) {
+        if constexpr (ADAM) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            *reinterpret_cast<f64x2*>(M + mo + (uint64_t)r * half) = f64x2{q[2 * r], q[2 * r + 1]};
+        }
+        const f32x4 sv = {s[0], s[1], s[2], s[3]};
+        *reinterpret_cast<f32x4*>(R + so) = sv;
+      } else {
+        if constexpr (ADAM) M[mo] = q[0], M[mo + width] = q[1];
+        R[so] = s[0];
+      }
+    }
+  }
+}
+
 unsigned grid_for(uint64_t blocks) {
   const uint64_t cap = (uint64_t)max_stream_blocks();
   if (blocks > cap) blocks = cap;
@@ -578,22 +776,175 @@ int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) 
   return PSG_OK;
 }
 
-// Both passes' front half: resolve q into t->slots, reject a bad list before
-// anything is written, insert the absent keys.
-int resolve_request(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
+// The front half of a request in three steps.  resolve_first: q into t->slots
+// and the request flags into t->flags_host; nothing is written to the table.
+int resolve_first(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
   PSG_TRY(ensure_slots(t, n));
-  PSG_TRY(resolve(t, keys, n, st));
-  const int* f = t->flags_host;
-  PSG_REQUIRE(!f[R_UNSORTED], PSG_ERR_INVALID,
-              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
-  PSG_REQUIRE(!f[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
+  return resolve(t, keys, n, st);
+}
+
+int require_in_range(const psg_table* t) {
+  PSG_REQUIRE(!t->flags_host[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
               (unsigned long long)t->key_begin, (unsigned long long)t->key_end);
-  if (f[R_MISSING]) {
+  return PSG_OK;
+}
+
+// resolve_finish: a strictly ascending list in range — insert its absent keys.
+int resolve_finish(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
+  if (t->flags_host[R_MISSING]) {
     PSG_TRY(insert_missing(t, keys, n, st));
     PSG_TRY(resolve(t, keys, n, st));
     PSG_REQUIRE(!t->flags_host[R_MISSING], PSG_ERR_HIP, "psg_table: a key is absent after its insert");
   }
   return PSG_OK;
+}
+
+// The strict calls: resolve q into t->slots, reject a bad list before anything
+// is written, insert the absent keys.
+int resolve_request(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
+  PSG_TRY(resolve_first(t, keys, n, st));
+  PSG_REQUIRE(!t->flags_host[R_UNSORTED], PSG_ERR_INVALID,
+              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
+  PSG_TRY(require_in_range(t));
+  return resolve_finish(t, keys, n, st);
+}
+
+// ---- the order-preserving request ---------------------------------------------
+struct AnyScratch {
+  uint64_t *k0, *k1;       // the sort's key buffers; afterwards the sorted keys and U
+  uint32_t *p0, *p1;       // the sort's position buffers; afterwards perm
+  uint32_t *seg, *counts;  // seg[n + 1]; radix counts, then the head counts per tile
+};
+
+int any_scratch(psg_table* t, uint64_t n, AnyScratch* a) {
+  auto al = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
+  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  const uint64_t u64n = al(n * 8), u32n = al(n * 4), segb = al((n + 1) * 4);
+  const uint64_t cnt = al(std::max<uint64_t>(radix_counts_elems(n), ntiles + 1) * 4);
+  const uint64_t bytes = 2 * u64n + 2 * u32n + segb + cnt;
+  if (t->any_bytes < bytes) {
+    if (t->any_buf) PSG_HIP(hipFree(t->any_buf));
+    t->any_buf = nullptr;
+    t->any_bytes = 0;
+    const uint64_t cap = std::max<uint64_t>(bytes + bytes / 2, 1 << 20);
+    PSG_HIP(hipMalloc(&t->any_buf, cap));
+    t->any_bytes = cap;
+  }
+  char* p = (char*)t->any_buf;
+  a->k0 = (uint64_t*)p, p += u64n;
+  a->k1 = (uint64_t*)p, p += u64n;
+  a->p0 = (uint32_t*)p, p += u32n;
+  a->p1 = (uint32_t*)p, p += u32n;
+  a->seg = (uint32_t*)p, p += segb;
+  a->counts = (uint32_t*)p;
+  return PSG_OK;
+}
+
+int bit_width(uint64_t x) { return x ? 64 - __builtin_clzll(x) : 0; }
+
+struct AnyPlan {  // the request as unique rows: slots in t->slots[m]
+  uint64_t m;
+  const uint32_t *seg, *perm;
+};
+
+// A list in range that is not strictly ascending: sort (key, position) stably,
+// cut the runs of equal keys, resolve the unique list as a strict request.
+int plan_any(psg_table* t, const uint64_t* keys, uint64_t n, AnyPlan* plan, hipStream_t st) {
+  AnyScratch a;
+  PSG_TRY(any_scratch(t, n, &a));
+  // the sort permutes its key buffer: a copy, the caller's keys are never written
+  PSG_HIP(hipMemcpyAsync(a.k0, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  int res = 0;
+  const int bits = std::max(1, bit_width(t->key_end - 1));  // every key is below key_end
+  PSG_TRY(radix_sort_u64(a.k0, a.p0, n, bits, true, a.k1, a.p1, a.counts, st, &res));
+  const uint64_t* sorted = res ? a.k1 : a.k0;
+  uint64_t* U = res ? a.k0 : a.k1;
+  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  k_rows_tile_heads<<<(unsigned)ntiles, kBlock, 0, st>>>(sorted, n, a.counts);
+  k_rows_scan_counts<<<1, kBlock, 0, st>>>(a.counts, ntiles);
+  k_rows_compact_heads<<<(unsigned)ntiles, kBlock, 0, st>>>(sorted, n, a.counts, ntiles, U, a.seg);
+  PSG_HIP(hipGetLastError());
+  uint32_t m32 = 0;
+  PSG_HIP(hipMemcpyAsync(&m32, a.counts + ntiles, sizeof(m32), hipMemcpyDeviceToHost, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  PSG_REQUIRE(m32 >= 1 && m32 <= n, PSG_ERR_HIP, "psg_table: %u unique keys in a list of %llu", m32,
+              (unsigned long long)n);
+  PSG_TRY(resolve_request(t, U, m32, st));
+  plan->m = m32;
+  plan->seg = a.seg;
+  plan->perm = res ? a.p1 : a.p0;
+  return PSG_OK;
+}
+
+template <int DT, bool VEC>
+int launch_apply_seg(psg_table* t, int op, const AnyPlan& p, const void* vals, void* out, hipStream_t st) {
+  using U = typename Unit<DT, VEC>::U;
+  const uint32_t upr = VEC ? t->width / Elem<DT>::kVec : t->width;
+  const uint32_t rpt = rows_per_tile(upr);
+  const unsigned g = grid_for((p.m + rpt - 1) / rpt);
+  U* R = (U*)t->rows;
+  switch (op) {
+    case PSG_PUSH:
+      k_rows_apply_seg<DT, PSG_PUSH, VEC>
+          <<<g, kBlock, 0, st>>>(R, t->slots, p.seg, p.perm, (const U*)vals, (U*)out, p.m, upr, rpt);
+      break;
+    case PSG_PULL:
+      k_rows_apply_seg<DT, PSG_PULL, VEC>
+          <<<g, kBlock, 0, st>>>(R, t->slots, p.seg, p.perm, (const U*)vals, (U*)out, p.m, upr, rpt);
+      break;
+    default:
+      k_rows_apply_seg<DT, PSG_PUSH | PSG_PULL, VEC>
+          <<<g, kBlock, 0, st>>>(R, t->slots, p.seg, p.perm, (const U*)vals, (U*)out, p.m, upr, rpt);
+  }
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+template <int DT>
+int apply_seg_dtype(psg_table* t, int op, const AnyPlan& p, const void* vals, void* out, hipStream_t st) {
+  // 16-B vectors under the condition of apply_dtype
+  const bool vec = ((uint64_t)t->width * t->esize) % 16 == 0 && (!(op & PSG_PUSH) || aligned16(vals)) &&
+                   (!(op & PSG_PULL) || aligned16(out));
+  return vec ? launch_apply_seg<DT, true>(t, op, p, vals, out, st) : launch_apply_seg<DT, false>(t, op, p, vals, out, st);
+}
+
+int apply_seg(psg_table* t, int op, const AnyPlan& p, const void* vals, void* out, hipStream_t st) {
+  switch (t->dtype) {
+    case PSG_F32: return apply_seg_dtype<PSG_F32>(t, op, p, vals, out, st);
+    case PSG_F64: return apply_seg_dtype<PSG_F64>(t, op, p, vals, out, st);
+    case PSG_F16: return apply_seg_dtype<PSG_F16>(t, op, p, vals, out, st);
+    default: return apply_seg_dtype<PSG_BF16>(t, op, p, vals, out, st);
+  }
+}
+
+template <bool ADAM, bool VEC>
+int launch_update_seg(psg_table* t, int op, const AnyPlan& p, const float* grads, float* out, float lr,
+                      const AdamArgs& a, hipStream_t st) {
+  const uint32_t upr = VEC ? t->width / 4 : t->width;
+  const uint32_t rpt = rows_per_tile(upr);
+  const unsigned g = grid_for((p.m + rpt - 1) / rpt);
+  float* R = (float*)t->rows;
+  if (op == PSG_PUSH)
+    k_rows_update_seg<ADAM, PSG_PUSH, VEC>
+        <<<g, kBlock, 0, st>>>(R, t->mom, t->slots, p.seg, p.perm, grads, out, p.m, upr, rpt, t->width, lr, a);
+  else
+    k_rows_update_seg<ADAM, PSG_PUSH | PSG_PULL, VEC>
+        <<<g, kBlock, 0, st>>>(R, t->mom, t->slots, p.seg, p.perm, grads, out, p.m, upr, rpt, t->width, lr, a);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+int update_seg(psg_table* t, int op, const AnyPlan& p, const float* grads, float* out, float lr, int iteration,
+               hipStream_t st) {
+  // 16-B vectors under the condition of update; c1 and c2 once for the request
+  const bool vec = t->width % 4 == 0 && aligned16(grads) && (!(op & PSG_PULL) || aligned16(out));
+  AdamArgs a = {};
+  if (!t->adam) return vec ? launch_update_seg<false, true>(t, op, p, grads, out, lr, a, st)
+                           : launch_update_seg<false, false>(t, op, p, grads, out, lr, a, st);
+  a = {t->alr, t->beta1, t->beta2, t->eps, 1 - std::pow(t->beta1, iteration + 1),
+       1 - std::pow(t->beta2, iteration + 1)};
+  return vec ? launch_update_seg<true, true>(t, op, p, grads, out, lr, a, st)
+             : launch_update_seg<true, false>(t, op, p, grads, out, lr, a, st);
 }
 
 }  // namespace
@@ -646,6 +997,7 @@ int psg_table_destroy(psg_table* t) {
   if (t->keys) (void)hipFree(t->keys);
   if (t->slots) (void)hipFree(t->slots);
   if (t->mom) (void)hipFree(t->mom);
+  if (t->any_buf) (void)hipFree(t->any_buf);
   if (t->flags_host) (void)hipHostFree(t->flags_host);
   delete t;
   return PSG_OK;
@@ -684,6 +1036,31 @@ int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* 
   PSG_TRY(resolve_request(t, keys, n, st));
   PSG_TRY(apply(t, flags, vals, out, n, st));
   // complete on return: keys and vals no longer read, a Pull's reply in memory
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+int psg_table_handle_any(psg_table* t, int flags, const uint64_t* keys, const void* vals, void* out, uint64_t n,
+                         psg_stream stream) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_handle_any: null table");
+  PSG_REQUIRE(flags >= 1 && flags <= 3, PSG_ERR_INVALID, "psg_table_handle_any: bad flags %d", flags);
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_handle_any: null keys");
+  PSG_REQUIRE(!(flags & PSG_PUSH) || vals, PSG_ERR_INVALID, "push without vals");
+  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_handle_any: more than 2^32-2 keys in one request");
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(resolve_first(t, keys, n, st));
+  PSG_TRY(require_in_range(t));
+  if (!t->flags_host[R_UNSORTED]) {  // strictly ascending: psg_table_handle's path
+    PSG_TRY(resolve_finish(t, keys, n, st));
+    PSG_TRY(apply(t, flags, vals, out, n, st));
+  } else {
+    AnyPlan plan;
+    PSG_TRY(plan_any(t, keys, n, &plan, st));
+    PSG_TRY(apply_seg(t, flags, plan, vals, out, st));
+  }
+  // complete on return, as psg_table_handle
   PSG_HIP(hipStreamSynchronize(st));
   return PSG_OK;
 }
@@ -739,6 +1116,34 @@ int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float*
   hipStream_t st = (hipStream_t)stream;
   PSG_TRY(resolve_request(t, keys, n, st));
   PSG_TRY(update(t, flags, grads, out, n, lr, iteration, st));
+  // complete on return, as psg_table_handle
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const float* grads, float* out, uint64_t n,
+                         float lr, int iteration, psg_stream stream) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_update_any: null table");
+  PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
+              "psg_table_update_any: flags %d are neither PUSH nor PUSH|PULL", flags);
+  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "psg_table_update_any: iteration %d below 0", iteration);
+  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "psg_table_update_any: the update is built for F32 tables");
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_update_any: null keys");
+  PSG_REQUIRE(grads, PSG_ERR_INVALID, "psg_table_update_any: null grads");
+  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_update_any: more than 2^32-2 keys in one request");
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(resolve_first(t, keys, n, st));
+  PSG_TRY(require_in_range(t));
+  if (!t->flags_host[R_UNSORTED]) {  // strictly ascending: psg_table_update's path
+    PSG_TRY(resolve_finish(t, keys, n, st));
+    PSG_TRY(update(t, flags, grads, out, n, lr, iteration, st));
+  } else {
+    AnyPlan plan;
+    PSG_TRY(plan_any(t, keys, n, &plan, st));
+    PSG_TRY(update_seg(t, flags, plan, grads, out, lr, iteration, st));
+  }
   // complete on return, as psg_table_handle
   PSG_HIP(hipStreamSynchronize(st));
   return PSG_OK;

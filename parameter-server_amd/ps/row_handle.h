@@ -11,10 +11,11 @@
 //   Pull:  res.vals[i * width + j] = row(key_i)[j]    (post-update)
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first
-// request; an absent key is inserted with a zero row.  Keys must be strictly
-// ascending (the KVPairs contract, KVApp.h:23): a list out of order or with
-// repeats fails the request's CHECK, where the scalar default handle serves
-// it in arrival order.  Register with KVServer::SetDeviceRequestHandle, so
+// request; an absent key is inserted with a zero row.  By default keys must be
+// strictly ascending (the KVPairs contract, KVApp.h:23): a list out of order or
+// with repeats fails the request's CHECK.  With any_order set the handle calls
+// psg_table_handle_any, which serves such a list in arrival order, every
+// occurrence of a key on its own, as the scalar default handle does.  Register with KVServer::SetDeviceRequestHandle, so
 // HBM frames are read in place; host frames are staged into HBM.  The handle
 // has no run handle: every request is served on its own, and workers slice
 // their key lists for real.
@@ -30,15 +31,17 @@ struct KVServerRowHandle {
   struct State {
     psg_table* table = nullptr;
     uint32_t width = 0;
+    bool any_order = false;
     ~State() {
       if (table) psg_table_destroy(table);
     }
   };
   std::shared_ptr<State> state = std::make_shared<State>();
 
-  explicit KVServerRowHandle(uint32_t width) {
+  explicit KVServerRowHandle(uint32_t width, bool any_order = false) {
     CHECK(width >= 1 && width <= 4096) << "KVServerRowHandle: width " << width << " outside [1, 4096]";
     state->width = width;
+    state->any_order = any_order;
   }
 
   void operator()(const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<Value>* server) {
@@ -71,8 +74,12 @@ struct KVServerRowHandle {
       }
       stage::Scope t(req_meta.push ? "server.handle.rows.push" : "server.handle.rows.pull");
       // returns once keys and vals are no longer read and the reply is in memory
-      device::Check(psg_table_handle(state->table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
-                    "psg_table_handle");
+      if (state->any_order)
+        device::Check(psg_table_handle_any(state->table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
+                      "psg_table_handle_any");
+      else
+        device::Check(psg_table_handle(state->table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
+                      "psg_table_handle");
     }
     if (req_meta.pull) {
       res.keys = req_data.keys;

@@ -20,8 +20,11 @@
 // an absent key starts from a zero row and zero moments.  Adam gets
 // ((double)learning_rate, 0.9, 0.999, 1e-8), as LRServer.h:83-84 constructs it.
 // The iteration is the server's one counter, as in the reference: there is no
-// per-row step count.  Keys must be strictly ascending (KVApp.h:23).  Register
-// with KVServer::SetDeviceRequestHandle; host frames are staged into HBM.
+// per-row step count.  Keys must be strictly ascending (KVApp.h:23) unless the
+// handle was built with any_order, when it calls psg_table_update_any /
+// psg_table_handle_any and every occurrence of a key is applied in arrival
+// order with the request's one iteration.  Register with
+// KVServer::SetDeviceRequestHandle; host frames are staged into HBM.
 #pragma once
 #include <memory>
 
@@ -38,19 +41,22 @@ struct KVServerRowOptHandle {
     float lr = 0.01f;
     bool use_adam = false;
     int iteration = 0;
+    bool any_order = false;
     ~State() {
       if (table) psg_table_destroy(table);
     }
   };
   std::shared_ptr<State> state = std::make_shared<State>();
 
-  KVServerRowOptHandle(uint32_t width, float learning_rate, bool use_adam, int start_iteration = 0) {
+  KVServerRowOptHandle(uint32_t width, float learning_rate, bool use_adam, int start_iteration = 0,
+                       bool any_order = false) {
     CHECK(width >= 1 && width <= 4096) << "KVServerRowOptHandle: width " << width << " outside [1, 4096]";
     CHECK_GE(start_iteration, 0);
     state->width = width;
     state->lr = learning_rate;
     state->use_adam = use_adam;
     state->iteration = start_iteration;
+    state->any_order = any_order;
   }
 
   void operator()(const KVMeta& req_meta, const KVPairs<float>& req_data, KVServer<float>* server) {
@@ -91,12 +97,13 @@ struct KVServerRowOptHandle {
                                     : accumulate ? "server.handle.rows.push" : "server.handle.rows.update");
       // both return once keys and vals are no longer read and the reply is in memory
       if (req_meta.push && !accumulate)
-        device::Check(psg_table_update(st.table, flags, dkeys.data(), dvals.data(), dout.data(), n, st.lr,
-                                       st.iteration, s),
-                      "psg_table_update");
+        device::Check((st.any_order ? psg_table_update_any : psg_table_update)(
+                          st.table, flags, dkeys.data(), dvals.data(), dout.data(), n, st.lr, st.iteration, s),
+                      st.any_order ? "psg_table_update_any" : "psg_table_update");
       else
-        device::Check(psg_table_handle(st.table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
-                      "psg_table_handle");
+        device::Check((st.any_order ? psg_table_handle_any : psg_table_handle)(st.table, flags, dkeys.data(),
+                                                                               dvals.data(), dout.data(), n, s),
+                      st.any_order ? "psg_table_handle_any" : "psg_table_handle");
     }
     // LRServer.h:193-195: worker 0's Push with cmd 1 ends an iteration
     if (req_meta.push && req_meta.cmd == 1 && req_meta.sender == PostOffice::WorkerRankToID(0)) ++st.iteration;

@@ -49,6 +49,7 @@ EXPORTS = [
     "psg_store_run_status", "psg_store_set_key_range",
     "psg_table_create", "psg_table_destroy", "psg_table_get_info", "psg_table_clear", "psg_table_handle",
     "psg_table_dump", "psg_table_set_adam", "psg_table_update", "psg_table_dump_moments",
+    "psg_table_handle_any", "psg_table_update_any",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
     "psg_comm_push_pull", "psg_comm_push_keyed", "psg_comm_pull_keyed",
@@ -155,6 +156,8 @@ def lib() -> C.CDLL:
             "psg_table_set_adam": ([vp, f64, f64, f64, f64], i32),
             "psg_table_update": ([vp, i32, vp, vp, vp, u64, f32, i32, vp], i32),
             "psg_table_dump_moments": ([vp, vp, vp], i32),
+            "psg_table_handle_any": ([vp, i32, vp, vp, vp, u64, vp], i32),
+            "psg_table_update_any": ([vp, i32, vp, vp, vp, u64, f32, i32, vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -525,6 +528,11 @@ class Table:
         """keys: n ascending device keys; vals / out: n * width elements."""
         _call("psg_table_handle", self.h, flags, _ptr(keys), _ptr(vals), _ptr(out), n, _s(stream))
 
+    def handle_any(self, flags: int, keys, vals, out, n: int, stream=None) -> None:
+        """handle() for n device keys in any order and with repeats
+        (psg_table_handle_any): the result of the n one-key requests in arrival order."""
+        _call("psg_table_handle_any", self.h, flags, _ptr(keys), _ptr(vals), _ptr(out), n, _s(stream))
+
     def clear(self, stream=None) -> None:
         _call("psg_table_clear", self.h, _s(stream))
 
@@ -544,6 +552,12 @@ class Table:
         """One gradient request (psg_table_update): SGD, or Adam after set_adam, on
         the rows of n ascending device keys; grads / out: n * width floats."""
         _call("psg_table_update", self.h, flags, _ptr(keys), _ptr(grads), _ptr(out), n, lr, iteration, _s(stream))
+
+    def update_any(self, flags: int, keys, grads, out, n: int, lr: float, iteration: int, stream=None) -> None:
+        """update() for n device keys in any order and with repeats
+        (psg_table_update_any): every occurrence is applied in arrival order."""
+        _call("psg_table_update_any", self.h, flags, _ptr(keys), _ptr(grads), _ptr(out), n, lr, iteration,
+              _s(stream))
 
     def dump_moments(self):
         """(m, v), each shaped (size, width), in key order."""
