@@ -180,6 +180,104 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total)
   *total = tot;
   return off + x - v;
 }
+
+// ---- ordered compaction -------------------------------------------------------
+// The positions i < n with pred(i), in order: compact_count leaves the hits
+// before each 1024-position tile in counts[tile] and their number in
+// counts[ntiles] (read_count brings it to the host); compact_emit then calls
+// emit(i, pos) for the pos-th hit and, once, emit.done(total).  A lane owns 4
+// consecutive positions, so the order inside a tile is kept.  pred and emit are
+// small functors passed by value; counts holds compact_tiles(n) + 1 words.
+constexpr int kCompactTile = 1024;
+constexpr int kCompactPerLane = kCompactTile / kBlock;
+inline uint64_t compact_tiles(uint64_t n) { return (n + kCompactTile - 1) / kCompactTile; }
+
+template <typename Pred>
+__device__ __forceinline__ uint32_t tile_hits(uint64_t i0, uint64_t n, const Pred& pred) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kCompactPerLane; ++k)
+    if (i0 + k < n && pred(i0 + k)) c++;
+  return c;
+}
+
+template <typename Pred>
+__global__ __launch_bounds__(256) void k_tile_count(uint64_t n, uint32_t* __restrict__ counts, Pred pred) {
+  const uint64_t i0 = (uint64_t)blockIdx.x * kCompactTile + (uint64_t)threadIdx.x * kCompactPerLane;
+  uint32_t tot;
+  block_excl_scan(tile_hits(i0, n, pred), &tot);
+  if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+}
+
+// Exclusive scan of the per-tile counts, single block (ntiles is small: n / 1024).
+// A template only so that a file that compacts nothing does not carry the kernel.
+template <typename = void>
+__global__ __launch_bounds__(256) void k_scan_counts(uint32_t* __restrict__ counts, uint64_t ntiles) {
+  __shared__ uint32_t carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (uint64_t b = 0; b < ntiles; b += kBlock) {
+    const uint64_t i = b + threadIdx.x;
+    const uint32_t v = i < ntiles ? counts[i] : 0;
+    uint32_t tot;
+    const uint32_t ex = block_excl_scan(v, &tot);
+    if (i < ntiles) counts[i] = carry + ex;
+    __syncthreads();
+    if (threadIdx.x == 0) carry += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) counts[ntiles] = carry;  // the total
+}
+
+template <typename Pred, typename Emit>
+__global__ __launch_bounds__(256) void k_tile_emit(uint64_t n, const uint32_t* __restrict__ offs, Pred pred,
+                                                   Emit emit) {
+  const uint64_t i0 = (uint64_t)blockIdx.x * kCompactTile + (uint64_t)threadIdx.x * kCompactPerLane;
+  uint32_t tot;
+  uint32_t pos = offs[blockIdx.x] + block_excl_scan(tile_hits(i0, n, pred), &tot);
+#pragma unroll
+  for (int k = 0; k < kCompactPerLane; ++k)
+    if (i0 + k < n && pred(i0 + k)) emit(i0 + k, pos++);
+  if (blockIdx.x == 0 && threadIdx.x == 0) emit.done(offs[gridDim.x]);
+}
+
+template <typename Pred>
+inline void compact_count(uint64_t n, uint32_t* counts, Pred pred, hipStream_t st) {
+  const uint64_t ntiles = compact_tiles(n);
+  k_tile_count<<<(unsigned)ntiles, kBlock, 0, st>>>(n, counts, pred);
+  k_scan_counts<><<<1, kBlock, 0, st>>>(counts, ntiles);
+}
+
+template <typename Pred, typename Emit>
+inline void compact_emit(uint64_t n, const uint32_t* counts, Pred pred, Emit emit, hipStream_t st) {
+  k_tile_emit<<<(unsigned)compact_tiles(n), kBlock, 0, st>>>(n, counts, pred, emit);
+}
+
+// The total compact_count left at counts[ntiles]; waits for the stream.
+inline int read_count(const uint32_t* dev, uint64_t* out, hipStream_t st) {
+  uint32_t m32 = 0;
+  PSG_HIP(hipMemcpyAsync(&m32, dev, sizeof(m32), hipMemcpyDeviceToHost, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  *out = m32;
+  return PSG_OK;
+}
+
+// The predicates and the plain emit of the two tables.
+struct SlotIs {  // slots[i] == what (a table's mark for an absent key)
+  const uint32_t* slots;
+  uint32_t what;
+  __device__ bool operator()(uint64_t i) const { return slots[i] == what; }
+};
+struct RunHead {  // a[i] opens a run of equal keys in the sorted a
+  const uint64_t* a;
+  __device__ bool operator()(uint64_t i) const { return i == 0 || a[i - 1] != a[i]; }
+};
+struct EmitKey {  // dst = the hit keys
+  const uint64_t* src;
+  uint64_t* dst;
+  __device__ void operator()(uint64_t i, uint32_t pos) const { dst[pos] = src[i]; }
+  __device__ void done(uint32_t) const {}
+};
 #endif
 
 // Bytes to hipMalloc for an array a peer process may map (hipIpc): the HIP

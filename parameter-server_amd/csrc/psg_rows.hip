@@ -18,18 +18,25 @@
 //                    (UINT32_MAX: absent) and the request flags.  The host
 //                    reads the flags (one synchronisation), rejects the request
 //                    before anything was written, or inserts the absent keys
-//                    and resolves again.
-//   k_rows_apply     the rows: lanes run over a tile's rows as one flat stream
+//                    (compact_count / compact_emit, psg_internal.h) and
+//                    resolves again.
+//   k_rows_walk      the rows: lanes run over a tile's rows as one flat stream
 //                    of 16-B vectors (rows of a multiple of 16 B) or of single
 //                    elements, so consecutive slots read and write consecutive
 //                    memory; one writer per row (keys are unique): no atomics.
+//                    What is done to a row is the walk's unit type: AccUnit
+//                    (row += vals) or OptUnit (the optimizer update).
 // Algorithmic bytes per f32 key of a Push: key 8 + slot 4 + 4 + 12 * width.
+// A list that is not strictly ascending (psg_table_*_any) is sorted, cut into
+// its unique keys and their occurrences (plan_any) and served by
+// k_rows_walk_seg, the same units over each unique row's occurrences.
+// serve() is the body of all four request calls.
 //
-// The optimizer update (psg_table_update) is the same two passes with
-// k_rows_update in place of k_rows_apply: the async-mode LRServer handle
-// (tests/src/LRServer.h:179-189) with SGD or Adam (tests/src/Adam.h:28-34) on
-// the rows a gradient Push names.  The Adam moments are f64 rows beside the
-// value rows, one array M[S x 2 width] in slot order: a row's m values, then
+// The optimizer update (psg_table_update) is the same two passes on OptUnit:
+// the async-mode LRServer handle (tests/src/LRServer.h:179-189) with SGD or
+// Adam (tests/src/Adam.h:28-34) on the rows a gradient Push names.  The Adam
+// moments are f64 rows beside the value rows, one array M[S x 2 width] in slot
+// order: a row's m values, then
 // its v values, so one row's state is one contiguous run and an insert moves
 // it with one k_rows_move of `width` 16-B units through the same slot map.
 // Where width is a multiple of 4 each half is kept in the lane order of the
@@ -37,6 +44,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "psg_internal.h"
@@ -71,7 +79,7 @@ namespace {
 constexpr int kRowTile = 1024;  // request keys per block of the resolve (4 per lane)
 constexpr uint32_t kAbsent = 0xffffffffu;
 constexpr uint64_t kMaxRows = 0xfffffffeull;
-// vectors (or elements) one block of k_rows_apply / k_rows_move serves per tile
+// vectors (or elements) one block of k_rows_walk / k_rows_move serves per tile
 constexpr uint32_t kUnitsPerTile = 2048;
 constexpr int kUnroll = 4;  // loads a lane keeps in flight
 
@@ -125,53 +133,6 @@ __global__ __launch_bounds__(256) void k_rows_resolve(const uint64_t* __restrict
   raise(flags, R_MISSING, missing != 0);
   raise(flags, R_RANGE, range != 0);
   raise(flags, R_UNSORTED, unsorted != 0);
-}
-
-// ---- absent keys, in order, into miss[] (counts per tile, scan, compaction) ----
-__global__ __launch_bounds__(256) void k_rows_tile_missing(const uint32_t* __restrict__ slots, uint64_t n,
-                                                           uint32_t* __restrict__ counts) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kRowTile / kBlock; ++k)
-    if (i0 + k < n && slots[i0 + k] == kAbsent) c++;
-  uint32_t tot;
-  block_excl_scan(c, &tot);
-  if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(256) void k_rows_scan_counts(uint32_t* __restrict__ counts, uint64_t ntiles) {
-  __shared__ uint32_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (uint64_t b = 0; b < ntiles; b += kBlock) {
-    const uint64_t i = b + threadIdx.x;
-    const uint32_t v = i < ntiles ? counts[i] : 0;
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan(v, &tot);
-    if (i < ntiles) counts[i] = carry + ex;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[ntiles] = carry;  // the total: keys absent
-}
-
-__global__ __launch_bounds__(256) void k_rows_compact_missing(const uint64_t* __restrict__ q,
-                                                              const uint32_t* __restrict__ slots, uint64_t n,
-                                                              const uint32_t* __restrict__ offs,
-                                                              uint64_t* __restrict__ miss) {
-  // each lane owns 4 consecutive keys so the order inside the tile is kept
-  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kRowTile / kBlock; ++k)
-    if (i0 + k < n && slots[i0 + k] == kAbsent) c++;
-  uint32_t tot;
-  uint32_t pos = offs[blockIdx.x] + block_excl_scan(c, &tot);
-#pragma unroll
-  for (int k = 0; k < kRowTile / kBlock; ++k)
-    if (i0 + k < n && slots[i0 + k] == kAbsent) miss[pos++] = q[i0 + k];
 }
 
 // Merge, keys: old row j goes to j + #(new keys < K[j]), new key t to
@@ -247,53 +208,38 @@ template <int DT> struct Unit<DT, false> {
   __device__ static inline U add(U a, U b) { return Elem<DT>::add1(a, b); }
 };
 
-// Pass 2.  Request row i (slot slots[i]) for i < n; every slot is present.
-template <int DT, int OP, bool VEC>
-__global__ __launch_bounds__(256) void k_rows_apply(typename Unit<DT, VEC>::U* __restrict__ R,
-                                                    const uint32_t* __restrict__ slots,
-                                                    const typename Unit<DT, VEC>::U* __restrict__ vals,
-                                                    typename Unit<DT, VEC>::U* __restrict__ out, uint64_t n,
-                                                    uint32_t upr, uint32_t rpt) {
+// ---- the row units --------------------------------------------------------------
+// What a lane holds of one row while it serves it.  A unit is a 16-B vector
+// (VEC) or one element, column c of the row in slot `slot`; R, the request's
+// values and its reply are arrays of that type U, so every offset counts units.
+// The two walks below are written against these members:
+//   Params, kDepth  the launch's constants; units a lane of the strict walk
+//                   keeps in flight
+//   locate          the unit's offsets
+//   load_state      the unit of the table's row (and of its moments)
+//   load_grad       the unit a request row carries (pushed values or gradients)
+//   step            one occurrence applied to the registers
+//   store_state     the registers back to the table
+//   reply           the registers to a request row's reply
+
+// Accumulate (psg_table_handle): row += vals, per dtype.
+template <int DT, bool VEC> struct AccUnit {
   using UT = Unit<DT, VEC>;
   using U = typename UT::U;
-  const uint64_t ntiles = (n + rpt - 1) / rpt;
-  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const uint64_t i0 = t * rpt;
-    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
-    const uint32_t total = nr * upr;
-    RowWalk w(threadIdx.x, upr);
-    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += kUnroll * kBlock) {
-      uint64_t so[kUnroll], ro[kUnroll];
-      bool ok[kUnroll];
-      U s[kUnroll], v[kUnroll];
-#pragma unroll
-      for (int k = 0; k < kUnroll; ++k) {
-        ok[k] = e0 + (uint32_t)k * kBlock < total;
-        if (ok[k]) {
-          const uint64_t i = i0 + w.r;
-          so[k] = (uint64_t)slots[i] * upr + w.c;
-          ro[k] = i * upr + w.c;
-        }
-        w.next();
-      }
-#pragma unroll
-      for (int k = 0; k < kUnroll; ++k) {
-        if (!ok[k]) continue;
-        s[k] = R[so[k]];
-        if constexpr ((OP & PSG_PUSH) != 0) v[k] = vals[ro[k]];
-      }
-#pragma unroll
-      for (int k = 0; k < kUnroll; ++k) {
-        if (!ok[k]) continue;
-        if constexpr ((OP & PSG_PUSH) != 0) {
-          s[k] = UT::add(s[k], v[k]);
-          R[so[k]] = s[k];
-        }
-        if constexpr ((OP & PSG_PULL) != 0) out[ro[k]] = s[k];
-      }
-    }
+  struct Params {};
+  static constexpr int kDepth = kUnroll;
+  static constexpr bool kPullAlone = true;  // a Pull without a Push is served
+  uint64_t so;
+  U s;
+  __device__ __forceinline__ void locate(uint64_t slot, uint32_t c, uint32_t upr, const Params&) {
+    so = slot * upr + c;
   }
-}
+  __device__ __forceinline__ void load_state(const U* R, const double*, const Params&) { s = R[so]; }
+  __device__ static __forceinline__ U load_grad(const U* vals, uint64_t ro) { return vals[ro]; }
+  __device__ __forceinline__ void step(U v, const Params&) { s = UT::add(s, v); }
+  __device__ __forceinline__ void store_state(U* R, double*, const Params&) const { R[so] = s; }
+  __device__ __forceinline__ void reply(U* out, uint64_t ro) const { out[ro] = s; }
+};
 
 // ---- the optimizer update ----------------------------------------------------
 // Where in its half (m or v) of a moment row the moment of column j lives.
@@ -313,23 +259,106 @@ struct AdamArgs {
   double alr, b1, b2, eps, c1, c2;
 };
 
-// Pass 2 of psg_table_update.  Request row i (slot slots[i]) for i < n; every
-// slot is present.  Per element (LRServer.h:182-189, Adam.h:28-34):
+// Optimize (psg_table_update), F32 rows.  Per element (LRServer.h:182-189,
+// Adam.h:28-34):
 //   g = (double)(lr * grad); Adam: m, v updated, g = alr * (m / c1) / (sqrt(v / c2) + eps);
 //   row = (float)((double)row - g); the Pull's reply is the updated row.
 // VEC: a unit is four columns (16 B of gradient, 16 B of row, four 16-B moment
-// pairs); else one column.  Every load of a step is issued before its
-// arithmetic; SGD keeps kUnroll units in flight, Adam two (24 data registers a
-// unit and the f64 divide and square root on top).
-template <bool ADAM, int OP, bool VEC>
-__global__ __launch_bounds__(256) void k_rows_update(float* __restrict__ R, double* __restrict__ M,
-                                                     const uint32_t* __restrict__ slots,
-                                                     const float* __restrict__ grads, float* __restrict__ out,
-                                                     uint64_t n, uint32_t upr, uint32_t rpt, uint32_t width, float lr,
-                                                     AdamArgs a) {
-  constexpr int E = VEC ? 4 : 1;
-  constexpr int UN = ADAM ? 2 : kUnroll;
-  const uint32_t half = width / 2;
+// pairs in the mom_col layout); else one column.  SGD keeps kUnroll units in
+// flight, Adam two (24 data registers a unit and the f64 divide and square
+// root on top).  This is the one copy of the arithmetic: it matches the
+// reference bit for bit, in this operation order and without contraction.
+template <bool ADAM, bool VEC> struct OptUnit {
+  static constexpr int E = VEC ? 4 : 1;
+  typedef typename std::conditional<VEC, f32x4, float>::type U;
+  struct Params {
+    uint32_t width;
+    float lr;
+    AdamArgs a;
+  };
+  static constexpr int kDepth = ADAM ? 2 : kUnroll;
+  static constexpr bool kPullAlone = false;
+  float s[E];
+  double q[2 * E];  // m of the unit's columns, then v
+  uint64_t so, mo;  // offsets of the unit: row (units), m (doubles)
+  __device__ __forceinline__ void locate(uint64_t slot, uint32_t c, uint32_t upr, const Params& p) {
+    so = slot * upr + c;
+    if constexpr (ADAM) mo = slot * 2 * p.width + (VEC ? 2 * c : mom_col(c, p.width));
+  }
+  __device__ __forceinline__ void load_state(const U* R, const double* M, const Params& p) {
+    if constexpr (VEC) {
+      const f32x4 sv = R[so];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = sv[e];
+      if constexpr (ADAM) {
+        const uint32_t half = p.width / 2;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const f64x2 pr = *reinterpret_cast<const f64x2*>(M + mo + (uint64_t)r * half);
+          q[2 * r] = pr[0], q[2 * r + 1] = pr[1];
+        }
+      }
+    } else {
+      s[0] = R[so];
+      if constexpr (ADAM) q[0] = M[mo], q[1] = M[mo + p.width];
+    }
+  }
+  __device__ static __forceinline__ U load_grad(const U* grads, uint64_t ro) { return grads[ro]; }
+  __device__ __forceinline__ void step(U gu, const Params& p) {
+    const float lr = p.lr;
+    const AdamArgs& a = p.a;
+    float g[E];
+    if constexpr (VEC) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = gu[e];
+    } else {
+      g[0] = gu;
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      double gr = (double)(lr * g[e]);
+      if constexpr (ADAM) {
+        const double mi = a.b1 * q[e] + (1.0 - a.b1) * gr;
+        const double vi = a.b2 * q[E + e] + (1.0 - a.b2) * gr * gr;
+        q[e] = mi;
+        q[E + e] = vi;
+        gr = a.alr * (mi / a.c1) / (sqrt(vi / a.c2) + a.eps);
+      }
+      s[e] = (float)((double)s[e] - gr);
+    }
+  }
+  __device__ __forceinline__ U packed() const {
+    if constexpr (VEC) return f32x4{s[0], s[1], s[2], s[3]};
+    else return s[0];
+  }
+  __device__ __forceinline__ void store_state(U* R, double* M, const Params& p) const {
+    if constexpr (ADAM) {
+      if constexpr (VEC) {
+        const uint32_t half = p.width / 2;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          *reinterpret_cast<f64x2*>(M + mo + (uint64_t)r * half) = f64x2{q[2 * r], q[2 * r + 1]};
+      } else {
+        M[mo] = q[0], M[mo + p.width] = q[1];
+      }
+    }
+    R[so] = packed();
+  }
+  __device__ __forceinline__ void reply(U* out, uint64_t ro) const { out[ro] = packed(); }
+};
+
+// ---- the two walks --------------------------------------------------------------
+// Pass 2 of the strict calls.  Request row i (slot slots[i]) for i < n; every
+// slot is present.  Lanes run over a tile's rows as one flat stream of units,
+// kDepth of them in flight: every load of a step is issued before its
+// arithmetic.  One writer per row (keys are unique): no atomics.
+template <typename UNIT, int OP>
+__global__ __launch_bounds__(256) void k_rows_walk(typename UNIT::U* __restrict__ R, double* __restrict__ M,
+                                                   const uint32_t* __restrict__ slots,
+                                                   const typename UNIT::U* __restrict__ vals,
+                                                   typename UNIT::U* __restrict__ out, uint64_t n, uint32_t upr,
+                                                   uint32_t rpt, typename UNIT::Params prm) {
+  constexpr int UN = UNIT::kDepth;
   const uint64_t ntiles = (n + rpt - 1) / rpt;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const uint64_t i0 = t * rpt;
@@ -337,72 +366,36 @@ __global__ __launch_bounds__(256) void k_rows_update(float* __restrict__ R, doub
     const uint32_t total = nr * upr;
     RowWalk w(threadIdx.x, upr);
     for (uint32_t e0 = threadIdx.x; e0 < total; e0 += UN * kBlock) {
-      uint64_t so[UN], ro[UN], mo[UN];  // offsets of the unit: row (floats), request (floats), m (doubles)
+      // u and ro start from zero: left unset, a unit past the tile's end would
+      // carry the last step's registers around the loop (6 more VGPRs for Adam)
+      UNIT u[UN] = {};
+      typename UNIT::U g[UN];
+      uint64_t ro[UN] = {};  // the unit's offset in the request
       bool ok[UN];
-      float s[UN][E], g[UN][E];
-      double q[UN][2 * E];  // m of the unit's columns, then v
 #pragma unroll
       for (int k = 0; k < UN; ++k) {
         ok[k] = e0 + (uint32_t)k * kBlock < total;
         if (ok[k]) {
           const uint64_t i = i0 + w.r;
-          const uint64_t slot = slots[i];
-          so[k] = (slot * upr + w.c) * E;
-          ro[k] = (i * upr + w.c) * E;
-          if constexpr (ADAM) mo[k] = slot * 2 * width + (VEC ? 2 * w.c : mom_col(w.c, width));
+          u[k].locate(slots[i], w.c, upr, prm);
+          ro[k] = i * upr + w.c;
         }
         w.next();
       }
 #pragma unroll
       for (int k = 0; k < UN; ++k) {
         if (!ok[k]) continue;
-        if constexpr (VEC) {
-          const f32x4 sv = *reinterpret_cast<const f32x4*>(R + so[k]);
-          const f32x4 gv = *reinterpret_cast<const f32x4*>(grads + ro[k]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s[k][e] = sv[e], g[k][e] = gv[e];
-          if constexpr (ADAM) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const f64x2 p = *reinterpret_cast<const f64x2*>(M + mo[k] + (uint64_t)r * half);
-              q[k][2 * r] = p[0], q[k][2 * r + 1] = p[1];
-            }
-          }
-        } else {
-          s[k][0] = R[so[k]];
-          g[k][0] = grads[ro[k]];
-          if constexpr (ADAM) q[k][0] = M[mo[k]], q[k][1] = M[mo[k] + width];
-        }
+        u[k].load_state(R, M, prm);
+        if constexpr ((OP & PSG_PUSH) != 0) g[k] = UNIT::load_grad(vals, ro[k]);
       }
 #pragma unroll
       for (int k = 0; k < UN; ++k) {
         if (!ok[k]) continue;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          double gr = (double)(lr * g[k][e]);
-          if constexpr (ADAM) {
-            const double mi = a.b1 * q[k][e] + (1.0 - a.b1) * gr;
-            const double vi = a.b2 * q[k][E + e] + (1.0 - a.b2) * gr * gr;
-            q[k][e] = mi;
-            q[k][E + e] = vi;
-            gr = a.alr * (mi / a.c1) / (sqrt(vi / a.c2) + a.eps);
-          }
-          s[k][e] = (float)((double)s[k][e] - gr);
+        if constexpr ((OP & PSG_PUSH) != 0) {
+          u[k].step(g[k], prm);
+          u[k].store_state(R, M, prm);
         }
-        if constexpr (VEC) {
-          if constexpr (ADAM) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              *reinterpret_cast<f64x2*>(M + mo[k] + (uint64_t)r * half) = f64x2{q[k][2 * r], q[k][2 * r + 1]};
-          }
-          const f32x4 sv = {s[k][0], s[k][1], s[k][2], s[k][3]};
-          *reinterpret_cast<f32x4*>(R + so[k]) = sv;
-          if constexpr ((OP & PSG_PULL) != 0) *reinterpret_cast<f32x4*>(out + ro[k]) = sv;
-        } else {
-          if constexpr (ADAM) M[mo[k]] = q[k][0], M[mo[k] + width] = q[k][1];
-          R[so[k]] = s[k][0];
-          if constexpr ((OP & PSG_PULL) != 0) out[ro[k]] = s[k][0];
-        }
+        if constexpr ((OP & PSG_PULL) != 0) u[k].reply(out, ro[k]);
       }
     }
   }
@@ -410,63 +403,37 @@ __global__ __launch_bounds__(256) void k_rows_update(float* __restrict__ R, doub
 
 // ---- the order-preserving request (psg_table_*_any) ---------------------------
 // The list is sorted stably by key with its positions (radix_sort_u64, iota):
-// sorted[n] and perm[n].  The heads of the runs of equal keys give the strictly
-// ascending unique list U[m] and seg[m + 1], the bounds of each key's
-// occurrences in perm — in arrival order, the sort being stable.  Same tiles as
-// the missing-key compaction above: 1024 positions a block, 4 a lane.
-__device__ __forceinline__ bool seg_head(const uint64_t* __restrict__ sorted, uint64_t i) {
-  return i == 0 || sorted[i - 1] != sorted[i];
-}
+// sorted[n] and perm[n].  The heads of the runs of equal keys (RunHead) give
+// the strictly ascending unique list U[m] and seg[m + 1], the bounds of each
+// key's occurrences in perm — in arrival order, the sort being stable.
+struct EmitHead {
+  const uint64_t* sorted;
+  uint64_t n;
+  uint64_t* U;
+  uint32_t* seg;
+  __device__ void operator()(uint64_t i, uint32_t pos) const {
+    U[pos] = sorted[i];
+    seg[pos] = (uint32_t)i;
+  }
+  __device__ void done(uint32_t m) const { seg[m] = (uint32_t)n; }
+};
 
-__global__ __launch_bounds__(256) void k_rows_tile_heads(const uint64_t* __restrict__ sorted, uint64_t n,
-                                                         uint32_t* __restrict__ counts) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kRowTile / kBlock; ++k)
-    if (i0 + k < n && seg_head(sorted, i0 + k)) c++;
-  uint32_t tot;
-  block_excl_scan(c, &tot);
-  if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-
-// offs: the scanned tile counts, offs[ntiles] = m
-__global__ __launch_bounds__(256) void k_rows_compact_heads(const uint64_t* __restrict__ sorted, uint64_t n,
-                                                            const uint32_t* __restrict__ offs, uint64_t ntiles,
-                                                            uint64_t* __restrict__ U, uint32_t* __restrict__ seg) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kRowTile + (uint64_t)threadIdx.x * (kRowTile / kBlock);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kRowTile / kBlock; ++k)
-    if (i0 + k < n && seg_head(sorted, i0 + k)) c++;
-  uint32_t tot;
-  uint32_t pos = offs[blockIdx.x] + block_excl_scan(c, &tot);
-#pragma unroll
-  for (int k = 0; k < kRowTile / kBlock; ++k)
-    if (i0 + k < n && seg_head(sorted, i0 + k)) {
-      U[pos] = sorted[i0 + k];
-      seg[pos++] = (uint32_t)(i0 + k);
-    }
-  if (blockIdx.x == 0 && threadIdx.x == 0) seg[offs[ntiles]] = (uint32_t)n;
-}
-
-// Pass 2 of psg_table_handle_any.  Unique row u (slot slots[u]) for u < m; its
+// Pass 2 of the any-order calls.  Unique row u (slot slots[u]) for u < m; its
 // occurrences are request rows perm[seg[u] .. seg[u + 1]), in arrival order.
-// The lanes walk the unique rows as k_rows_apply walks request rows; a lane
-// loads its unit of the row once, runs over the occurrences (add, reply with
-// the running row) and stores the unit once: one writer per row, no atomics.
-// The loop is a chain perm -> vals -> add; the position two ahead and the
-// values one ahead are loaded before the current add.
-template <int DT, int OP, bool VEC>
-__global__ __launch_bounds__(256) void k_rows_apply_seg(typename Unit<DT, VEC>::U* __restrict__ R,
-                                                        const uint32_t* __restrict__ slots,
-                                                        const uint32_t* __restrict__ seg,
-                                                        const uint32_t* __restrict__ perm,
-                                                        const typename Unit<DT, VEC>::U* __restrict__ vals,
-                                                        typename Unit<DT, VEC>::U* __restrict__ out, uint64_t m,
-                                                        uint32_t upr, uint32_t rpt) {
-  using UT = Unit<DT, VEC>;
-  using U = typename UT::U;
+// The lanes walk the unique rows as k_rows_walk walks request rows; a lane
+// loads its unit of the row (and its moments) once, runs over the occurrences
+// (step, reply with the running row) and stores the unit once: one writer per
+// row, no atomics.  The loop is a chain perm -> vals -> step; the position two
+// ahead and the values one ahead are loaded before the current step.
+template <typename UNIT, int OP>
+__global__ __launch_bounds__(256) void k_rows_walk_seg(typename UNIT::U* __restrict__ R, double* __restrict__ M,
+                                                       const uint32_t* __restrict__ slots,
+                                                       const uint32_t* __restrict__ seg,
+                                                       const uint32_t* __restrict__ perm,
+                                                       const typename UNIT::U* __restrict__ vals,
+                                                       typename UNIT::U* __restrict__ out, uint64_t m, uint32_t upr,
+                                                       uint32_t rpt, typename UNIT::Params prm) {
+  using U = typename UNIT::U;
   const uint64_t ntiles = (m + rpt - 1) / rpt;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const uint64_t u0 = t * rpt;
@@ -475,129 +442,26 @@ __global__ __launch_bounds__(256) void k_rows_apply_seg(typename Unit<DT, VEC>::
     RowWalk w(threadIdx.x, upr);
     for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
       const uint64_t u = u0 + w.r;
-      const uint64_t so = (uint64_t)slots[u] * upr + w.c;
+      UNIT x;
+      x.locate(slots[u], w.c, upr, prm);
       uint32_t p = seg[u];
       const uint32_t pe = seg[u + 1];  // > p: every unique key has an occurrence
-      U s = R[so];
+      x.load_state(R, M, prm);
       uint32_t i0 = perm[p];
       uint32_t i1 = p + 1 < pe ? perm[p + 1] : 0;
       U v = {};
-      if constexpr ((OP & PSG_PUSH) != 0) v = vals[(uint64_t)i0 * upr + w.c];
+      if constexpr ((OP & PSG_PUSH) != 0) v = UNIT::load_grad(vals, (uint64_t)i0 * upr + w.c);
       for (; p < pe; ++p) {
         const uint32_t i2 = p + 2 < pe ? perm[p + 2] : 0;
         U vn = v;
         if constexpr ((OP & PSG_PUSH) != 0) {
-          if (p + 1 < pe) vn = vals[(uint64_t)i1 * upr + w.c];
-          s = UT::add(s, v);
+          if (p + 1 < pe) vn = UNIT::load_grad(vals, (uint64_t)i1 * upr + w.c);
+          x.step(v, prm);
         }
-        if constexpr ((OP & PSG_PULL) != 0) out[(uint64_t)i0 * upr + w.c] = s;
+        if constexpr ((OP & PSG_PULL) != 0) x.reply(out, (uint64_t)i0 * upr + w.c);
         i0 = i1, i1 = i2, v = vn;
       }
-      if constexpr ((OP & PSG_PUSH) != 0) R[so] = s;
-    }
-  }
-}
-
-// Pass 2 of psg_table_update_any: k_rows_update's arithmetic, expression for
-// expression, on the occurrences of each unique row in arrival order.  A lane
-// keeps its unit of the row and its moment pairs (the table's mom_col layout)
-// in registers over the segment and stores them once; the next occurrence's
-// gradients are loaded before the current one's arithmetic.
-template <bool ADAM, int OP, bool VEC>
-__global__ __launch_bounds__(256) void k_rows_update_seg(float* __restrict__ R, double* __restrict__ M,
-                                                         const uint32_t* __restrict__ slots,
-                                                         const uint32_t* __restrict__ seg,
-                                                         const uint32_t* __restrict__ perm,
-                                                         const float* __restrict__ grads, float* __restrict__ out,
-                                                         uint64_t m, uint32_t upr, uint32_t rpt, uint32_t width,
-                                                         float lr, AdamArgs a) {
-  constexpr int E = VEC ? 4 : 1;
-  const uint32_t half = width / 2;
-  const uint64_t ntiles = (m + rpt - 1) / rpt;
-  auto load_g = [&](float (&g)[E], uint32_t i, uint32_t c) {
-    const uint64_t ro = ((uint64_t)i * upr + c) * E;
-    if constexpr (VEC) {
-      const f32x4 gv = *reinterpret_cast<const f32x4*>(grads + ro);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] = gv[e];
-    } else {
-      g[0] = grads[ro];
-    }
-  };
-  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const uint64_t u0 = t * rpt;
-    const uint32_t nr = (uint32_t)(m - u0 < rpt ? m - u0 : rpt);
-    const uint32_t total = nr * upr;
-    RowWalk w(threadIdx.x, upr);
-    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += kBlock, w.next()) {
-      const uint64_t u = u0 + w.r;
-      const uint64_t slot = slots[u];
-      const uint64_t so = (slot * upr + w.c) * E;
-      const uint64_t mo = slot * 2 * width + (VEC ? 2 * w.c : mom_col(w.c, width));
-      uint32_t p = seg[u];
-      const uint32_t pe = seg[u + 1];  // > p
-      float s[E], g[E], gn[E];
-      double q[2 * E];  // m of the unit's columns, then v
-      if constexpr (VEC) {
-        const f32x4 sv = *reinterpret_cast<const f32x4*>(R + so);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] = sv[e];
-        if constexpr (ADAM) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const f64x2 pr = *reinterpret_cast<const f64x2*>(M + mo + (uint64_t)r * half);
-            q[2 * r] = pr[0], q[2 * r + 1] = pr[1];
-          }
-        }
-      } else {
-        s[0] = R[so];
-        if constexpr (ADAM) q[0] = M[mo], q[1] = M[mo + width];
-      }
-      uint32_t i0 = perm[p];
-      uint32_t i1 = p + 1 < pe ? perm[p + 1] : 0;
-      load_g(g, i0, w.c);
-      for (; p < pe; ++p) {
-        const uint32_t i2 = p + 2 < pe ? perm[p + 2] : 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) gn[e] = g[e];
-        if (p + 1 < pe) load_g(gn, i1, w.c);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          double gr = (double)(lr * g[e]);
-          if constexpr (ADAM) {
-            const double mi = a.b1 * q[e] + (1.0 - a.b1) * gr;
-            const double vi = a.b2 * q[E + e] + (1.0 - a.b2) * gr * gr;
-            q[e] = mi;
-            q[E + e] = vi;
-            gr = a.alr * (mi / a.c1) / (sqrt(vi / a.c2) + a.eps);
-          }
-          s[e] = (float)((double)s[e] - gr);
-        }
-        if constexpr ((OP & PSG_PULL) != 0) {
-          const uint64_t ro = ((uint64_t)i0 * upr + w.c) * E;
-          if constexpr (VEC) {
-            const f32x4 sv = {s[0], s[1], s[2], s[3]};
-            *reinterpret_cast<f32x4*>(out + ro) = sv;
-          } else {
-            out[ro] = s[0];
-          }
-        }
-        i0 = i1, i1 = i2;
-#pragma unroll
-        for (int e = 0; e < E; ++e) g[e] = gn[e];
-      }
-      if constexpr (VEC) {
-        if constexpr (ADAM) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            *reinterpret_cast<f64x2*>(M + mo + (uint64_t)r * half) = f64x2{q[2 * r], q[2 * r + 1]};
-        }
-        const f32x4 sv = {s[0], s[1], s[2], s[3]};
-        *reinterpret_cast<f32x4*>(R + so) = sv;
-      } else {
-        if constexpr (ADAM) M[mo] = q[0], M[mo + width] = q[1];
-        R[so] = s[0];
-      }
+      if constexpr ((OP & PSG_PUSH) != 0) x.store_state(R, M, prm);
     }
   }
 }
@@ -606,75 +470,6 @@ unsigned grid_for(uint64_t blocks) {
   const uint64_t cap = (uint64_t)max_stream_blocks();
   if (blocks > cap) blocks = cap;
   return blocks ? (unsigned)blocks : 1u;
-}
-
-template <int DT, bool VEC>
-int launch_apply(psg_table* t, int op, const void* vals, void* out, uint64_t n, hipStream_t st) {
-  using U = typename Unit<DT, VEC>::U;
-  const uint32_t upr = VEC ? t->width / Elem<DT>::kVec : t->width;
-  const uint32_t rpt = rows_per_tile(upr);
-  const unsigned g = grid_for((n + rpt - 1) / rpt);
-  U* R = (U*)t->rows;
-  switch (op) {
-    case PSG_PUSH:
-      k_rows_apply<DT, PSG_PUSH, VEC><<<g, kBlock, 0, st>>>(R, t->slots, (const U*)vals, (U*)out, n, upr, rpt);
-      break;
-    case PSG_PULL:
-      k_rows_apply<DT, PSG_PULL, VEC><<<g, kBlock, 0, st>>>(R, t->slots, (const U*)vals, (U*)out, n, upr, rpt);
-      break;
-    default:
-      k_rows_apply<DT, PSG_PUSH | PSG_PULL, VEC><<<g, kBlock, 0, st>>>(R, t->slots, (const U*)vals, (U*)out, n, upr,
-                                                                      rpt);
-  }
-  PSG_HIP(hipGetLastError());
-  return PSG_OK;
-}
-
-template <int DT>
-int apply_dtype(psg_table* t, int op, const void* vals, void* out, uint64_t n, hipStream_t st) {
-  // 16-B vectors when every row, here and in the request, starts on 16 B
-  const bool vec = ((uint64_t)t->width * t->esize) % 16 == 0 && (!(op & PSG_PUSH) || aligned16(vals)) &&
-                   (!(op & PSG_PULL) || aligned16(out));
-  return vec ? launch_apply<DT, true>(t, op, vals, out, n, st) : launch_apply<DT, false>(t, op, vals, out, n, st);
-}
-
-int apply(psg_table* t, int op, const void* vals, void* out, uint64_t n, hipStream_t st) {
-  switch (t->dtype) {
-    case PSG_F32: return apply_dtype<PSG_F32>(t, op, vals, out, n, st);
-    case PSG_F64: return apply_dtype<PSG_F64>(t, op, vals, out, n, st);
-    case PSG_F16: return apply_dtype<PSG_F16>(t, op, vals, out, n, st);
-    default: return apply_dtype<PSG_BF16>(t, op, vals, out, n, st);
-  }
-}
-
-template <bool ADAM, bool VEC>
-int launch_update(psg_table* t, int op, const float* grads, float* out, uint64_t n, float lr, const AdamArgs& a,
-                  hipStream_t st) {
-  const uint32_t upr = VEC ? t->width / 4 : t->width;
-  const uint32_t rpt = rows_per_tile(upr);
-  const unsigned g = grid_for((n + rpt - 1) / rpt);
-  float* R = (float*)t->rows;
-  if (op == PSG_PUSH)
-    k_rows_update<ADAM, PSG_PUSH, VEC><<<g, kBlock, 0, st>>>(R, t->mom, t->slots, grads, out, n, upr, rpt, t->width, lr, a);
-  else
-    k_rows_update<ADAM, PSG_PUSH | PSG_PULL, VEC>
-        <<<g, kBlock, 0, st>>>(R, t->mom, t->slots, grads, out, n, upr, rpt, t->width, lr, a);
-  PSG_HIP(hipGetLastError());
-  return PSG_OK;
-}
-
-int update(psg_table* t, int op, const float* grads, float* out, uint64_t n, float lr, int iteration, hipStream_t st) {
-  // 16-B vectors when every row, here and in the request, starts on 16 B
-  const bool vec = t->width % 4 == 0 && aligned16(grads) && (!(op & PSG_PULL) || aligned16(out));
-  AdamArgs a = {};
-  if (!t->adam) return vec ? launch_update<false, true>(t, op, grads, out, n, lr, a, st)
-                           : launch_update<false, false>(t, op, grads, out, n, lr, a, st);
-  // the two bias corrections of Adam.h:31-32, with the host libm pow the
-  // reference calls (as psg_lr.hip)
-  a = {t->alr, t->beta1, t->beta2, t->eps, 1 - std::pow(t->beta1, iteration + 1),
-       1 - std::pow(t->beta2, iteration + 1)};
-  return vec ? launch_update<true, true>(t, op, grads, out, n, lr, a, st)
-             : launch_update<true, false>(t, op, grads, out, n, lr, a, st);
 }
 
 template <typename U>
@@ -726,16 +521,15 @@ struct DevBuf {  // a device scratch array freed on every return path
 
 // Insert the keys of q that t->slots marks absent, each with a zero row.
 int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) {
-  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  const uint64_t ntiles = compact_tiles(n);
+  const SlotIs absent = {t->slots, kAbsent};
   DevBuf counts, miss, old_to, new_to;
   PSG_HIP(hipMalloc(&counts.p, (ntiles + 1) * sizeof(uint32_t)));
-  k_rows_tile_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(t->slots, n, (uint32_t*)counts.p);
-  k_rows_scan_counts<<<1, kBlock, 0, st>>>((uint32_t*)counts.p, ntiles);
+  compact_count(n, (uint32_t*)counts.p, absent, st);
   PSG_HIP(hipGetLastError());
-  uint32_t m32 = 0;
-  PSG_HIP(hipMemcpyAsync(&m32, (uint32_t*)counts.p + ntiles, sizeof(m32), hipMemcpyDeviceToHost, st));
-  PSG_HIP(hipStreamSynchronize(st));
-  const uint64_t m = m32, S = t->size;
+  uint64_t m = 0;
+  PSG_TRY(read_count((const uint32_t*)counts.p + ntiles, &m, st));
+  const uint64_t S = t->size;
   if (m == 0) return PSG_OK;
   uint64_t cap = t->capacity;
   if (S + m > cap) cap = std::max<uint64_t>(std::max<uint64_t>(S + m, cap * 2), 1024);
@@ -745,8 +539,7 @@ int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) 
   PSG_HIP(hipMalloc(&miss.p, m * sizeof(uint64_t)));
   PSG_HIP(hipMalloc(&old_to.p, std::max<uint64_t>(S, 1) * sizeof(uint32_t)));
   PSG_HIP(hipMalloc(&new_to.p, m * sizeof(uint32_t)));
-  k_rows_compact_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(q, t->slots, n, (const uint32_t*)counts.p,
-                                                              (uint64_t*)miss.p);
+  compact_emit(n, (const uint32_t*)counts.p, absent, EmitKey{q, (uint64_t*)miss.p}, st);
   PSG_HIP(hipGetLastError());
   DevBuf K2, R2, M2;
   PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
@@ -783,6 +576,12 @@ int resolve_first(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st
   return resolve(t, keys, n, st);
 }
 
+int require_ascending(const psg_table* t) {
+  PSG_REQUIRE(!t->flags_host[R_UNSORTED], PSG_ERR_INVALID,
+              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
+  return PSG_OK;
+}
+
 int require_in_range(const psg_table* t) {
   PSG_REQUIRE(!t->flags_host[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
               (unsigned long long)t->key_begin, (unsigned long long)t->key_end);
@@ -799,12 +598,11 @@ int resolve_finish(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t s
   return PSG_OK;
 }
 
-// The strict calls: resolve q into t->slots, reject a bad list before anything
-// is written, insert the absent keys.
+// The three in a row, as a strict call does them: a bad list is rejected before
+// anything is written.  plan_any resolves its unique list this way.
 int resolve_request(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
   PSG_TRY(resolve_first(t, keys, n, st));
-  PSG_REQUIRE(!t->flags_host[R_UNSORTED], PSG_ERR_INVALID,
-              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
+  PSG_TRY(require_ascending(t));
   PSG_TRY(require_in_range(t));
   return resolve_finish(t, keys, n, st);
 }
@@ -818,7 +616,7 @@ struct AnyScratch {
 
 int any_scratch(psg_table* t, uint64_t n, AnyScratch* a) {
   auto al = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
-  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  const uint64_t ntiles = compact_tiles(n);
   const uint64_t u64n = al(n * 8), u32n = al(n * 4), segb = al((n + 1) * 4);
   const uint64_t cnt = al(std::max<uint64_t>(radix_counts_elems(n), ntiles + 1) * 4);
   const uint64_t bytes = 2 * u64n + 2 * u32n + segb + cnt;
@@ -859,92 +657,141 @@ int plan_any(psg_table* t, const uint64_t* keys, uint64_t n, AnyPlan* plan, hipS
   PSG_TRY(radix_sort_u64(a.k0, a.p0, n, bits, true, a.k1, a.p1, a.counts, st, &res));
   const uint64_t* sorted = res ? a.k1 : a.k0;
   uint64_t* U = res ? a.k0 : a.k1;
-  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
-  k_rows_tile_heads<<<(unsigned)ntiles, kBlock, 0, st>>>(sorted, n, a.counts);
-  k_rows_scan_counts<<<1, kBlock, 0, st>>>(a.counts, ntiles);
-  k_rows_compact_heads<<<(unsigned)ntiles, kBlock, 0, st>>>(sorted, n, a.counts, ntiles, U, a.seg);
+  compact_count(n, a.counts, RunHead{sorted}, st);
+  compact_emit(n, a.counts, RunHead{sorted}, EmitHead{sorted, n, U, a.seg}, st);
   PSG_HIP(hipGetLastError());
-  uint32_t m32 = 0;
-  PSG_HIP(hipMemcpyAsync(&m32, a.counts + ntiles, sizeof(m32), hipMemcpyDeviceToHost, st));
-  PSG_HIP(hipStreamSynchronize(st));
-  PSG_REQUIRE(m32 >= 1 && m32 <= n, PSG_ERR_HIP, "psg_table: %u unique keys in a list of %llu", m32,
+  uint64_t m = 0;
+  PSG_TRY(read_count(a.counts + compact_tiles(n), &m, st));
+  PSG_REQUIRE(m >= 1 && m <= n, PSG_ERR_HIP, "psg_table: %u unique keys in a list of %llu", (uint32_t)m,
               (unsigned long long)n);
-  PSG_TRY(resolve_request(t, U, m32, st));
-  plan->m = m32;
+  PSG_TRY(resolve_request(t, U, m, st));
+  plan->m = m;
   plan->seg = a.seg;
   plan->perm = res ? a.p1 : a.p0;
   return PSG_OK;
 }
 
-template <int DT, bool VEC>
-int launch_apply_seg(psg_table* t, int op, const AnyPlan& p, const void* vals, void* out, hipStream_t st) {
-  using U = typename Unit<DT, VEC>::U;
-  const uint32_t upr = VEC ? t->width / Elem<DT>::kVec : t->width;
+// ---- pass 2: the dispatch -----------------------------------------------------------
+// Either walk for one unit type and op: the strict one over the request's n
+// rows (plan null), or the segment walk over the plan's unique rows.
+template <typename UNIT, int OP>
+int launch_walk(psg_table* t, const AnyPlan* p, const void* vals, void* out, uint64_t n, uint32_t upr,
+                const typename UNIT::Params& prm, hipStream_t st) {
+  using U = typename UNIT::U;
   const uint32_t rpt = rows_per_tile(upr);
-  const unsigned g = grid_for((p.m + rpt - 1) / rpt);
-  U* R = (U*)t->rows;
-  switch (op) {
-    case PSG_PUSH:
-      k_rows_apply_seg<DT, PSG_PUSH, VEC>
-          <<<g, kBlock, 0, st>>>(R, t->slots, p.seg, p.perm, (const U*)vals, (U*)out, p.m, upr, rpt);
-      break;
-    case PSG_PULL:
-      k_rows_apply_seg<DT, PSG_PULL, VEC>
-          <<<g, kBlock, 0, st>>>(R, t->slots, p.seg, p.perm, (const U*)vals, (U*)out, p.m, upr, rpt);
-      break;
-    default:
-      k_rows_apply_seg<DT, PSG_PUSH | PSG_PULL, VEC>
-          <<<g, kBlock, 0, st>>>(R, t->slots, p.seg, p.perm, (const U*)vals, (U*)out, p.m, upr, rpt);
-  }
+  const uint64_t rows = p ? p->m : n;
+  const unsigned g = grid_for((rows + rpt - 1) / rpt);
+  if (p)
+    k_rows_walk_seg<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, (const U*)vals,
+                                                     (U*)out, rows, upr, rpt, prm);
+  else
+    k_rows_walk<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, (const U*)vals, (U*)out, rows, upr, rpt,
+                                                 prm);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
+}
+
+template <typename UNIT>
+int launch_op(psg_table* t, int op, const AnyPlan* p, const void* vals, void* out, uint64_t n, uint32_t upr,
+              const typename UNIT::Params& prm, hipStream_t st) {
+  if (op == PSG_PUSH) return launch_walk<UNIT, PSG_PUSH>(t, p, vals, out, n, upr, prm, st);
+  if constexpr (UNIT::kPullAlone)
+    if (op == PSG_PULL) return launch_walk<UNIT, PSG_PULL>(t, p, vals, out, n, upr, prm, st);
+  return launch_walk<UNIT, PSG_PUSH | PSG_PULL>(t, p, vals, out, n, upr, prm, st);
+}
+
+// 16-B vectors when every row, here and in the request, starts on 16 B
+bool accumulate_vec(const psg_table* t, int op, const void* vals, const void* out) {
+  return ((uint64_t)t->width * t->esize) % 16 == 0 && (!(op & PSG_PUSH) || aligned16(vals)) &&
+         (!(op & PSG_PULL) || aligned16(out));
+}
+
+bool optimize_vec(const psg_table* t, int op, const float* grads, const float* out) {
+  return t->width % 4 == 0 && aligned16(grads) && (!(op & PSG_PULL) || aligned16(out));
+}
+
+// The two bias corrections of Adam.h:31-32, once for the request, with the host
+// libm pow the reference calls (as psg_lr.hip).  Zeros for an SGD table.
+AdamArgs adam_args(const psg_table* t, int iteration) {
+  if (!t->adam) return {};
+  return {t->alr,  t->beta1, t->beta2, t->eps, 1 - std::pow(t->beta1, iteration + 1),
+          1 - std::pow(t->beta2, iteration + 1)};
 }
 
 template <int DT>
-int apply_seg_dtype(psg_table* t, int op, const AnyPlan& p, const void* vals, void* out, hipStream_t st) {
-  // 16-B vectors under the condition of apply_dtype
-  const bool vec = ((uint64_t)t->width * t->esize) % 16 == 0 && (!(op & PSG_PUSH) || aligned16(vals)) &&
-                   (!(op & PSG_PULL) || aligned16(out));
-  return vec ? launch_apply_seg<DT, true>(t, op, p, vals, out, st) : launch_apply_seg<DT, false>(t, op, p, vals, out, st);
+int accumulate_dtype(psg_table* t, int op, const AnyPlan* p, const void* vals, void* out, uint64_t n, hipStream_t st) {
+  if (accumulate_vec(t, op, vals, out))
+    return launch_op<AccUnit<DT, true>>(t, op, p, vals, out, n, t->width / Elem<DT>::kVec, {}, st);
+  return launch_op<AccUnit<DT, false>>(t, op, p, vals, out, n, t->width, {}, st);
 }
 
-int apply_seg(psg_table* t, int op, const AnyPlan& p, const void* vals, void* out, hipStream_t st) {
+int accumulate(psg_table* t, int op, const AnyPlan* p, const void* vals, void* out, uint64_t n, hipStream_t st) {
   switch (t->dtype) {
-    case PSG_F32: return apply_seg_dtype<PSG_F32>(t, op, p, vals, out, st);
-    case PSG_F64: return apply_seg_dtype<PSG_F64>(t, op, p, vals, out, st);
-    case PSG_F16: return apply_seg_dtype<PSG_F16>(t, op, p, vals, out, st);
-    default: return apply_seg_dtype<PSG_BF16>(t, op, p, vals, out, st);
+    case PSG_F32: return accumulate_dtype<PSG_F32>(t, op, p, vals, out, n, st);
+    case PSG_F64: return accumulate_dtype<PSG_F64>(t, op, p, vals, out, n, st);
+    case PSG_F16: return accumulate_dtype<PSG_F16>(t, op, p, vals, out, n, st);
+    default: return accumulate_dtype<PSG_BF16>(t, op, p, vals, out, n, st);
   }
 }
 
-template <bool ADAM, bool VEC>
-int launch_update_seg(psg_table* t, int op, const AnyPlan& p, const float* grads, float* out, float lr,
-                      const AdamArgs& a, hipStream_t st) {
-  const uint32_t upr = VEC ? t->width / 4 : t->width;
-  const uint32_t rpt = rows_per_tile(upr);
-  const unsigned g = grid_for((p.m + rpt - 1) / rpt);
-  float* R = (float*)t->rows;
-  if (op == PSG_PUSH)
-    k_rows_update_seg<ADAM, PSG_PUSH, VEC>
-        <<<g, kBlock, 0, st>>>(R, t->mom, t->slots, p.seg, p.perm, grads, out, p.m, upr, rpt, t->width, lr, a);
-  else
-    k_rows_update_seg<ADAM, PSG_PUSH | PSG_PULL, VEC>
-        <<<g, kBlock, 0, st>>>(R, t->mom, t->slots, p.seg, p.perm, grads, out, p.m, upr, rpt, t->width, lr, a);
-  PSG_HIP(hipGetLastError());
-  return PSG_OK;
+template <bool ADAM>
+int optimize_adam(psg_table* t, int op, const AnyPlan* p, const float* grads, float* out, uint64_t n, float lr,
+                  int iteration, hipStream_t st) {
+  if (optimize_vec(t, op, grads, out))
+    return launch_op<OptUnit<ADAM, true>>(t, op, p, grads, out, n, t->width / 4,
+                                          {t->width, lr, adam_args(t, iteration)}, st);
+  return launch_op<OptUnit<ADAM, false>>(t, op, p, grads, out, n, t->width, {t->width, lr, adam_args(t, iteration)},
+                                         st);
 }
 
-int update_seg(psg_table* t, int op, const AnyPlan& p, const float* grads, float* out, float lr, int iteration,
-               hipStream_t st) {
-  // 16-B vectors under the condition of update; c1 and c2 once for the request
-  const bool vec = t->width % 4 == 0 && aligned16(grads) && (!(op & PSG_PULL) || aligned16(out));
-  AdamArgs a = {};
-  if (!t->adam) return vec ? launch_update_seg<false, true>(t, op, p, grads, out, lr, a, st)
-                           : launch_update_seg<false, false>(t, op, p, grads, out, lr, a, st);
-  a = {t->alr, t->beta1, t->beta2, t->eps, 1 - std::pow(t->beta1, iteration + 1),
-       1 - std::pow(t->beta2, iteration + 1)};
-  return vec ? launch_update_seg<true, true>(t, op, p, grads, out, lr, a, st)
-             : launch_update_seg<true, false>(t, op, p, grads, out, lr, a, st);
+int optimize(psg_table* t, int op, const AnyPlan* p, const float* grads, float* out, uint64_t n, float lr,
+             int iteration, hipStream_t st) {
+  return t->adam ? optimize_adam<true>(t, op, p, grads, out, n, lr, iteration, st)
+                 : optimize_adam<false>(t, op, p, grads, out, n, lr, iteration, st);
+}
+
+// The body of the four request calls; `name` is the call's, for its messages.
+// opt: psg_table_update* (vals are gradients) instead of psg_table_handle*;
+// any: a list that is not strictly ascending is planned instead of rejected.
+int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const uint64_t* keys, const void* vals,
+          void* out, uint64_t n, float lr, int iteration, psg_stream stream) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  if (opt) {
+    PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
+                "%s: flags %d are neither PUSH nor PUSH|PULL", name, flags);
+    PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
+    PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
+  } else {
+    PSG_REQUIRE(flags >= 1 && flags <= 3, PSG_ERR_INVALID, "%s: bad flags %d", name, flags);
+  }
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
+  if (opt)
+    PSG_REQUIRE(vals, PSG_ERR_INVALID, "%s: null grads", name);
+  else
+    PSG_REQUIRE(!(flags & PSG_PUSH) || vals, PSG_ERR_INVALID, "push without vals");
+  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(resolve_first(t, keys, n, st));
+  // a strict call rejects a list out of order before it looks at the range
+  if (!any) PSG_TRY(require_ascending(t));
+  PSG_TRY(require_in_range(t));
+  AnyPlan plan;
+  const AnyPlan* p = nullptr;
+  if (t->flags_host[R_UNSORTED]) {
+    PSG_TRY(plan_any(t, keys, n, &plan, st));
+    p = &plan;
+  } else {
+    PSG_TRY(resolve_finish(t, keys, n, st));
+  }
+  if (opt)
+    PSG_TRY(optimize(t, flags, p, (const float*)vals, (float*)out, n, lr, iteration, st));
+  else
+    PSG_TRY(accumulate(t, flags, p, vals, out, n, st));
+  // complete on return: keys and vals no longer read, a Pull's reply in memory
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
 }
 
 }  // namespace
@@ -1025,44 +872,12 @@ int psg_table_clear(psg_table* t, psg_stream stream) {
 
 int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* vals, void* out, uint64_t n,
                      psg_stream stream) {
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_handle: null table");
-  PSG_REQUIRE(flags >= 1 && flags <= 3, PSG_ERR_INVALID, "psg_table_handle: bad flags %d", flags);
-  if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_handle: null keys");
-  PSG_REQUIRE(!(flags & PSG_PUSH) || vals, PSG_ERR_INVALID, "push without vals");
-  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_handle: more than 2^32-2 keys in one request");
-  hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(resolve_request(t, keys, n, st));
-  PSG_TRY(apply(t, flags, vals, out, n, st));
-  // complete on return: keys and vals no longer read, a Pull's reply in memory
-  PSG_HIP(hipStreamSynchronize(st));
-  return PSG_OK;
+  return serve("psg_table_handle", false, false, t, flags, keys, vals, out, n, 0.f, 0, stream);
 }
 
 int psg_table_handle_any(psg_table* t, int flags, const uint64_t* keys, const void* vals, void* out, uint64_t n,
                          psg_stream stream) {
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_handle_any: null table");
-  PSG_REQUIRE(flags >= 1 && flags <= 3, PSG_ERR_INVALID, "psg_table_handle_any: bad flags %d", flags);
-  if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_handle_any: null keys");
-  PSG_REQUIRE(!(flags & PSG_PUSH) || vals, PSG_ERR_INVALID, "push without vals");
-  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_handle_any: more than 2^32-2 keys in one request");
-  hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(resolve_first(t, keys, n, st));
-  PSG_TRY(require_in_range(t));
-  if (!t->flags_host[R_UNSORTED]) {  // strictly ascending: psg_table_handle's path
-    PSG_TRY(resolve_finish(t, keys, n, st));
-    PSG_TRY(apply(t, flags, vals, out, n, st));
-  } else {
-    AnyPlan plan;
-    PSG_TRY(plan_any(t, keys, n, &plan, st));
-    PSG_TRY(apply_seg(t, flags, plan, vals, out, st));
-  }
-  // complete on return, as psg_table_handle
-  PSG_HIP(hipStreamSynchronize(st));
-  return PSG_OK;
+  return serve("psg_table_handle_any", false, true, t, flags, keys, vals, out, n, 0.f, 0, stream);
 }
 
 int psg_table_dump(psg_table* t, uint64_t* keys_host, void* rows_host) {
@@ -1103,50 +918,12 @@ int psg_table_set_adam(psg_table* t, double learning_rate, double beta1, double 
 
 int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float* grads, float* out, uint64_t n,
                      float lr, int iteration, psg_stream stream) {
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_update: null table");
-  PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
-              "psg_table_update: flags %d are neither PUSH nor PUSH|PULL", flags);
-  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "psg_table_update: iteration %d below 0", iteration);
-  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "psg_table_update: the update is built for F32 tables");
-  if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_update: null keys");
-  PSG_REQUIRE(grads, PSG_ERR_INVALID, "psg_table_update: null grads");
-  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_update: more than 2^32-2 keys in one request");
-  hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(resolve_request(t, keys, n, st));
-  PSG_TRY(update(t, flags, grads, out, n, lr, iteration, st));
-  // complete on return, as psg_table_handle
-  PSG_HIP(hipStreamSynchronize(st));
-  return PSG_OK;
+  return serve("psg_table_update", true, false, t, flags, keys, grads, out, n, lr, iteration, stream);
 }
 
 int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const float* grads, float* out, uint64_t n,
                          float lr, int iteration, psg_stream stream) {
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_update_any: null table");
-  PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
-              "psg_table_update_any: flags %d are neither PUSH nor PUSH|PULL", flags);
-  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "psg_table_update_any: iteration %d below 0", iteration);
-  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "psg_table_update_any: the update is built for F32 tables");
-  if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_table_update_any: null keys");
-  PSG_REQUIRE(grads, PSG_ERR_INVALID, "psg_table_update_any: null grads");
-  PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "psg_table_update_any: more than 2^32-2 keys in one request");
-  hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(resolve_first(t, keys, n, st));
-  PSG_TRY(require_in_range(t));
-  if (!t->flags_host[R_UNSORTED]) {  // strictly ascending: psg_table_update's path
-    PSG_TRY(resolve_finish(t, keys, n, st));
-    PSG_TRY(update(t, flags, grads, out, n, lr, iteration, st));
-  } else {
-    AnyPlan plan;
-    PSG_TRY(plan_any(t, keys, n, &plan, st));
-    PSG_TRY(update_seg(t, flags, plan, grads, out, lr, iteration, st));
-  }
-  // complete on return, as psg_table_handle
-  PSG_HIP(hipStreamSynchronize(st));
-  return PSG_OK;
+  return serve("psg_table_update_any", true, true, t, flags, keys, grads, out, n, lr, iteration, stream);
 }
 
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {

@@ -1807,66 +1807,6 @@ __global__ __launch_bounds__(256) void k_slots_stretch(const uint32_t* __restric
   raise_flag(flags, F_MISSING, bad != 0);
 }
 
-// block_excl_scan: psg_internal.h
-
-// Pass 1 of the compaction: absent-key count per 1024-key tile.
-__global__ __launch_bounds__(256) void k_tile_missing(const uint32_t* __restrict__ slots, uint64_t n,
-                                                      uint32_t* __restrict__ counts) {
-  const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kTile / kBlock; ++k) {
-    uint64_t i = t0 + (uint64_t)k * kBlock + threadIdx.x;
-    if (i < n && slots[i] == kNoSlot) c++;
-  }
-  uint32_t tot;
-  block_excl_scan(c, &tot);
-  if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-
-// Exclusive scan of the per-tile counts, single block (ntiles is small:
-// n / 1024).
-__global__ __launch_bounds__(256) void k_scan_counts(uint32_t* __restrict__ counts, uint64_t ntiles) {
-  __shared__ uint32_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (uint64_t b = 0; b < ntiles; b += kBlock) {
-    uint64_t i = b + threadIdx.x;
-    uint32_t v = i < ntiles ? counts[i] : 0;
-    uint32_t tot;
-    uint32_t ex = block_excl_scan(v, &tot);
-    if (i < ntiles) counts[i] = carry + ex;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[ntiles] = carry;  // the total: keys absent
-}
-
-// Pass 2: write the absent keys, in order, to miss[].
-__global__ __launch_bounds__(256) void k_compact_missing(const uint64_t* __restrict__ q,
-                                                         const uint32_t* __restrict__ slots,
-                                                         uint64_t n,
-                                                         const uint32_t* __restrict__ offs,
-                                                         uint64_t* __restrict__ miss) {
-  const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
-  // each lane owns 4 consecutive keys so the order inside the tile is kept
-  const uint64_t i0 = t0 + (uint64_t)threadIdx.x * (kTile / kBlock);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kTile / kBlock; ++k) {
-    uint64_t i = i0 + k;
-    if (i < n && slots[i] == kNoSlot) c++;
-  }
-  uint32_t tot;
-  uint32_t pos = offs[blockIdx.x] + block_excl_scan(c, &tot);
-#pragma unroll
-  for (int k = 0; k < kTile / kBlock; ++k) {
-    uint64_t i = i0 + k;
-    if (i < n && slots[i] == kNoSlot) miss[pos++] = q[i];
-  }
-}
-
 // Merge: old element j goes to j + #(new keys < K[j]); new key t goes to
 // t + #(old keys < M[t]).
 template <typename T>
@@ -2106,22 +2046,20 @@ static int merge_insert(psg_store* s, const uint64_t* miss, uint64_t m, hipStrea
 }
 
 static int insert_missing(psg_store* s, const uint64_t* q, uint64_t n, hipStream_t st) {
-  const uint64_t ntiles = (n + kTile - 1) / kTile;
+  const uint64_t ntiles = compact_tiles(n);
+  const SlotIs absent = {s->slots, kNoSlot};
   uint32_t* counts = nullptr;
   uint64_t* miss = nullptr;
   PSG_HIP(hipMalloc((void**)&counts, (ntiles + 1) * sizeof(uint32_t)));
-  k_tile_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(s->slots, n, counts);
-  k_scan_counts<<<1, kBlock, 0, st>>>(counts, ntiles);
-  uint32_t m32 = 0;
-  PSG_HIP(hipMemcpyAsync(&m32, counts + ntiles, sizeof(m32), hipMemcpyDeviceToHost, st));
-  PSG_HIP(hipStreamSynchronize(st));
-  const uint64_t m = m32;
+  compact_count(n, counts, absent, st);
+  uint64_t m = 0;
+  PSG_TRY(read_count(counts + ntiles, &m, st));
   if (m == 0) {
     PSG_HIP(hipFree(counts));
     return PSG_OK;
   }
   PSG_HIP(hipMalloc((void**)&miss, m * sizeof(uint64_t)));
-  k_compact_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(q, s->slots, n, counts, miss);
+  compact_emit(n, counts, absent, EmitKey{q, miss}, st);
   PSG_HIP(hipGetLastError());
   int rc;
   switch (s->dtype) {
@@ -2252,38 +2190,6 @@ __global__ __launch_bounds__(256) void k_resolve_any(const uint64_t* __restrict_
   }
 }
 
-// first occurrences in a sorted array: per-1024-key-tile counts, then compaction
-__global__ __launch_bounds__(256) void k_tile_heads(const uint64_t* __restrict__ a, uint64_t n,
-                                                    uint32_t* __restrict__ counts) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * (kTile / kBlock);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kTile / kBlock; ++k) {
-    const uint64_t i = i0 + k;
-    if (i < n && (i == 0 || a[i - 1] != a[i])) c++;
-  }
-  uint32_t tot;
-  block_excl_scan(c, &tot);
-  if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(256) void k_compact_heads(const uint64_t* __restrict__ a, uint64_t n,
-                                                       const uint32_t* __restrict__ offs, uint64_t* __restrict__ out) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * (kTile / kBlock);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kTile / kBlock; ++k) {
-    const uint64_t i = i0 + k;
-    if (i < n && (i == 0 || a[i - 1] != a[i])) c++;
-  }
-  uint32_t tot;
-  uint32_t pos = offs[blockIdx.x] + block_excl_scan(c, &tot);
-#pragma unroll
-  for (int k = 0; k < kTile / kBlock; ++k) {
-    const uint64_t i = i0 + k;
-    if (i < n && (i == 0 || a[i - 1] != a[i])) out[pos++] = a[i];
-  }
-}
-
 // One lane per run of equal slots in the slot-sorted pairs (ss, sp): the
 // occurrences in arrival order, each added in turn (Push), each reply the
 // running value (PushPull).
@@ -2315,7 +2221,7 @@ struct GScratch {
 };
 static int general_scratch(psg_store* s, uint64_t n, GScratch* g) {
   auto al = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
-  const uint64_t nt = (n + kTile - 1) / kTile + 2;
+  const uint64_t nt = compact_tiles(n) + 2;
   const uint64_t u32n = al(n * 4), u64n = al(n * 8), cnt = al(radix_counts_elems(n) * 4), tc = al(nt * 4);
   const uint64_t bytes = 3 * u32n + cnt + tc + 2 * u64n;
   if (s->gbuf_bytes < bytes) {
@@ -2336,37 +2242,26 @@ static int general_scratch(psg_store* s, uint64_t n, GScratch* g) {
   return PSG_OK;
 }
 
-static int read_count(const uint32_t* dev, uint64_t* out, hipStream_t st) {
-  uint32_t m32 = 0;
-  PSG_HIP(hipMemcpyAsync(&m32, dev, sizeof(m32), hipMemcpyDeviceToHost, st));
-  PSG_HIP(hipStreamSynchronize(st));
-  *out = m32;
-  return PSG_OK;
-}
-
 // The absent keys of q[0..n) (s->slots[i] == kNoSlot; any order, repeats)
 // inserted with value 0 (operator[], KVApp.h:449/452): compacted, sorted,
 // made unique, merged into K.  *inserted = how many.
 static int insert_missing_any(psg_store* s, const uint64_t* q, uint64_t n, const GScratch& g, uint64_t* inserted,
                               hipStream_t st) {
   *inserted = 0;
-  const uint64_t ntiles = (n + kTile - 1) / kTile;
-  k_tile_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(s->slots, n, g.tcount);
-  k_scan_counts<<<1, kBlock, 0, st>>>(g.tcount, ntiles);
+  const SlotIs absent = {s->slots, kNoSlot};
+  compact_count(n, g.tcount, absent, st);
   uint64_t m = 0;
-  PSG_TRY(read_count(g.tcount + ntiles, &m, st));
+  PSG_TRY(read_count(g.tcount + compact_tiles(n), &m, st));
   if (m == 0) return PSG_OK;
-  k_compact_missing<<<(unsigned)ntiles, kBlock, 0, st>>>(q, s->slots, n, g.tcount, g.k0);
+  compact_emit(n, g.tcount, absent, EmitKey{q, g.k0}, st);
   int res = 0;
   PSG_TRY(radix_sort_u64(g.k0, g.a, m, 64, true, g.k1, g.b, g.counts, st, &res));
   const uint64_t* sorted = res ? g.k1 : g.k0;
   uint64_t* uniq = res ? g.k0 : g.k1;
-  const uint64_t mt = (m + kTile - 1) / kTile;
-  k_tile_heads<<<(unsigned)mt, kBlock, 0, st>>>(sorted, m, g.tcount);
-  k_scan_counts<<<1, kBlock, 0, st>>>(g.tcount, mt);
+  compact_count(m, g.tcount, RunHead{sorted}, st);
   uint64_t mu = 0;
-  PSG_TRY(read_count(g.tcount + mt, &mu, st));
-  k_compact_heads<<<(unsigned)mt, kBlock, 0, st>>>(sorted, m, g.tcount, uniq);
+  PSG_TRY(read_count(g.tcount + compact_tiles(m), &mu, st));
+  compact_emit(m, g.tcount, RunHead{sorted}, EmitKey{sorted, uniq}, st);
   PSG_HIP(hipGetLastError());
   switch (s->dtype) {
     case PSG_F32: PSG_TRY(merge_insert<float>(s, uniq, mu, st)); break;

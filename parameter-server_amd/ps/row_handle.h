@@ -26,6 +26,45 @@
 
 namespace ps {
 
+namespace detail {
+
+// The body the row handles share.  Stages the request's keys and values into
+// HBM, takes the worker's own output slice or allocates the reply, runs
+// call(stream, keys, vals, out) under a stage::Scope and answers.  call wraps a
+// psg_table_* request, which returns once keys and vals are no longer read and
+// the reply is in memory.
+template <typename Value, typename Call>
+void ServeRows(const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<Value>* server, size_t width,
+               const char* scope, Call call) {
+  const size_t n = req_data.keys.size();
+  const int dev = PostOffice::Get()->device();
+  KVPairs<Value> res;
+  SVector<Value> dout;
+  bool direct = false;
+  if (n && (req_meta.push || req_meta.pull)) {
+    psg_stream s = device::ThreadStream();
+    SVector<Key> dkeys = ToDeviceAsync(req_data.keys, dev);
+    SVector<Value> dvals;
+    if (req_meta.push) dvals = ToDeviceAsync(req_data.vals, dev);
+    if (req_meta.pull) {
+      // the worker's own output slice when it offered one of n * width
+      // values (written in place: no reply frame, no merge)
+      dout = server->TakeDirectOut(n * width);
+      direct = !dout.empty();
+      if (!direct) dout = SVector<Value>::OnDevice(n * width, dev);
+    }
+    stage::Scope t(scope);
+    call(s, dkeys.data(), dvals.data(), dout.data());
+  }
+  if (req_meta.pull) {
+    res.keys = req_data.keys;
+    if (!direct) res.vals = req_data.keys.on_device() ? dout : ToHost(dout);
+  }
+  server->Response(req_meta, res);
+}
+
+}  // namespace detail
+
 template <typename Value>
 struct KVServerRowHandle {
   struct State {
@@ -47,7 +86,6 @@ struct KVServerRowHandle {
   void operator()(const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<Value>* server) {
     const size_t n = req_data.keys.size();
     const size_t w = state->width;
-    KVPairs<Value> res;
     const int dev = PostOffice::Get()->device();
     CHECK_GE(dev, 0) << "KVServerRowHandle: the table lives in HBM and this node has no GPU";
     constexpr int dt = device::DType<Value>();
@@ -55,37 +93,18 @@ struct KVServerRowHandle {
     CHECK(req_data.lens.empty()) << "KVServerRowHandle: rows have one fixed width, lens are not supported";
     if (!state->table)
       device::Check(psg_table_create(dt, state->width, 0, kMaxKey, 0, &state->table), "psg_table_create");
-    const bool on_dev = req_data.keys.on_device();
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     if (req_meta.push) CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
-    SVector<Value> dout;
-    bool direct = false;
-    if (n && flags) {
-      psg_stream s = device::ThreadStream();
-      SVector<Key> dkeys = detail::ToDeviceAsync(req_data.keys, dev);
-      SVector<Value> dvals;
-      if (req_meta.push) dvals = detail::ToDeviceAsync(req_data.vals, dev);
-      if (req_meta.pull) {
-        // the worker's own output slice when it offered one of n * width
-        // values (written in place: no reply frame, no merge)
-        dout = server->TakeDirectOut(n * w);
-        direct = !dout.empty();
-        if (!direct) dout = SVector<Value>::OnDevice(n * w, dev);
-      }
-      stage::Scope t(req_meta.push ? "server.handle.rows.push" : "server.handle.rows.pull");
-      // returns once keys and vals are no longer read and the reply is in memory
-      if (state->any_order)
-        device::Check(psg_table_handle_any(state->table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
-                      "psg_table_handle_any");
-      else
-        device::Check(psg_table_handle(state->table, flags, dkeys.data(), dvals.data(), dout.data(), n, s),
-                      "psg_table_handle");
-    }
-    if (req_meta.pull) {
-      res.keys = req_data.keys;
-      if (!direct) res.vals = on_dev ? dout : detail::ToHost(dout);
-    }
-    server->Response(req_meta, res);
+    detail::ServeRows(req_meta, req_data, server, w,
+                      req_meta.push ? "server.handle.rows.push" : "server.handle.rows.pull",
+                      [&](psg_stream s, const Key* keys, const Value* vals, Value* out) {
+                        if (state->any_order)
+                          device::Check(psg_table_handle_any(state->table, flags, keys, vals, out, n, s),
+                                        "psg_table_handle_any");
+                        else
+                          device::Check(psg_table_handle(state->table, flags, keys, vals, out, n, s),
+                                        "psg_table_handle");
+                      });
   }
 };
 

@@ -28,7 +28,7 @@
 #pragma once
 #include <memory>
 
-#include "ps/kv_app.h"
+#include "ps/row_handle.h"
 
 namespace ps {
 
@@ -63,7 +63,6 @@ struct KVServerRowOptHandle {
     State& st = *state;
     const size_t n = req_data.keys.size();
     const size_t w = st.width;
-    KVPairs<float> res;
     const int dev = PostOffice::Get()->device();
     CHECK_GE(dev, 0) << "KVServerRowOptHandle: the table lives in HBM and this node has no GPU";
     CHECK(req_data.lens.empty()) << "KVServerRowOptHandle: rows have one fixed width, lens are not supported";
@@ -72,46 +71,28 @@ struct KVServerRowOptHandle {
       if (st.use_adam)
         device::Check(psg_table_set_adam(st.table, (double)st.lr, 0.9, 0.999, 1e-8), "psg_table_set_adam");
     }
-    const bool on_dev = req_data.keys.on_device();
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     const bool accumulate = req_meta.push && req_meta.cmd == kAccumulate;
     if (req_meta.push) {
       CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
       CHECK(req_meta.cmd >= 0 && req_meta.cmd <= kAccumulate) << "KVServerRowOptHandle: unknown Push cmd " << req_meta.cmd;
     }
-    SVector<float> dout;
-    bool direct = false;
-    if (n && flags) {
-      psg_stream s = device::ThreadStream();
-      SVector<Key> dkeys = detail::ToDeviceAsync(req_data.keys, dev);
-      SVector<float> dvals;
-      if (req_meta.push) dvals = detail::ToDeviceAsync(req_data.vals, dev);
-      if (req_meta.pull) {
-        // the worker's own output slice when it offered one of n * width
-        // values (written in place: no reply frame, no merge)
-        dout = server->TakeDirectOut(n * w);
-        direct = !dout.empty();
-        if (!direct) dout = SVector<float>::OnDevice(n * w, dev);
-      }
-      stage::Scope t(!req_meta.push ? "server.handle.rows.pull"
-                                    : accumulate ? "server.handle.rows.push" : "server.handle.rows.update");
-      // both return once keys and vals are no longer read and the reply is in memory
-      if (req_meta.push && !accumulate)
-        device::Check((st.any_order ? psg_table_update_any : psg_table_update)(
-                          st.table, flags, dkeys.data(), dvals.data(), dout.data(), n, st.lr, st.iteration, s),
-                      st.any_order ? "psg_table_update_any" : "psg_table_update");
-      else
-        device::Check((st.any_order ? psg_table_handle_any : psg_table_handle)(st.table, flags, dkeys.data(),
-                                                                               dvals.data(), dout.data(), n, s),
-                      st.any_order ? "psg_table_handle_any" : "psg_table_handle");
-    }
-    // LRServer.h:193-195: worker 0's Push with cmd 1 ends an iteration
-    if (req_meta.push && req_meta.cmd == 1 && req_meta.sender == PostOffice::WorkerRankToID(0)) ++st.iteration;
-    if (req_meta.pull) {
-      res.keys = req_data.keys;
-      if (!direct) res.vals = on_dev ? dout : detail::ToHost(dout);
-    }
-    server->Response(req_meta, res);
+    // LRServer.h:193-195: worker 0's Push with cmd 1 ends an iteration, once it is applied
+    const bool ends_iteration = req_meta.push && req_meta.cmd == 1 && req_meta.sender == PostOffice::WorkerRankToID(0);
+    if (ends_iteration && n == 0) ++st.iteration;  // nothing to apply: ServeRows makes no call
+    detail::ServeRows(
+        req_meta, req_data, server, w,
+        !req_meta.push ? "server.handle.rows.pull" : accumulate ? "server.handle.rows.push" : "server.handle.rows.update",
+        [&](psg_stream s, const Key* keys, const float* vals, float* out) {
+          if (req_meta.push && !accumulate)
+            device::Check((st.any_order ? psg_table_update_any : psg_table_update)(st.table, flags, keys, vals, out, n,
+                                                                                   st.lr, st.iteration, s),
+                          st.any_order ? "psg_table_update_any" : "psg_table_update");
+          else
+            device::Check((st.any_order ? psg_table_handle_any : psg_table_handle)(st.table, flags, keys, vals, out, n, s),
+                          st.any_order ? "psg_table_handle_any" : "psg_table_handle");
+          if (ends_iteration) ++st.iteration;
+        });
   }
 
   int iteration() const { return state->iteration; }
