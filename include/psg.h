@@ -18,6 +18,12 @@
  *   psg_table_*      the same store and loop for requests carrying k values
  *                    per key (rows), as DefaultSlicer slices them
  *                                                        src/ps/KVApp.h:515-574
+ *   psg_table_update / _update_any
+ *                    LRServer::RequestHandle async-mode update on rows
+ *                                                        tests/src/LRServer.h:179-189
+ *   psg_table_update_merged
+ *                    its sync-mode round on rows: k frames merged per key from
+ *                    zero, one optimizer step           tests/src/LRServer.h:151-178
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
  *   psg_slice        KVWorker<V>::DefaultSlicer           src/ps/KVApp.h:515-574
  *   psg_merge        the AddPullCB merge lambda           src/ps/KVApp.h:673-726
@@ -540,6 +546,43 @@ int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float*
  * psg_table_handle_any and psg_table_update. */
 int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const float* grads,
                          float* out, uint64_t n, float lr, int iteration, psg_stream stream);
+/* One sync-mode round (tests/src/LRServer.h:151-178) on rows: the gradients of
+ * k frames are merged per key from zero in arrival order, then the optimizer
+ * runs ONCE per key.  keys_host / grads_host / outs_host are host arrays of k
+ * DEVICE pointers (as psg_store_run, psg_lr_apply_sum), 1 <= k <= 16; frame j
+ * has ns_host[j] keys and ns_host[j] * width gradients.  Keys may come in any
+ * order and repeat, inside a frame and across frames; a frame may be empty
+ * (its pointers may then be NULL).  Arrival order is frame 0 .. k-1, position
+ * 0 .. ns[j]-1 inside a frame.  For every key K named anywhere, every column c:
+ *   float s = 0.0f;                                    // LRServer.h:155
+ *   for each occurrence (j, i) of K in arrival order:
+ *     s += grads_j[i*width + c];                       // one f32 add each, :159
+ *   double g = (double)(lr * s);                       // :167
+ *   Adam: m, v, g as in psg_table_update — the moments advance ONCE
+ *   row(K)[c] = (float)((double)row(K)[c] - g);
+ *   if (flags & PSG_PULL) outs_j[i*width + c] = row(K)[c] for EVERY occurrence
+ * The sum starts from +0.0f and the first add is kept (0.0f + -0.0f is +0.0f).
+ * This is what separates it from psg_table_update_any, which takes one step per
+ * occurrence.  c1 and c2 are evaluated once on the host from `iteration`.  An
+ * absent key is inserted once with a zero row and zero moments, then updated.
+ * flags: PSG_PUSH or PSG_PUSH | PSG_PULL; outs_host may be NULL for PSG_PUSH.
+ * F32 tables only (PSG_ERR_UNSUPPORTED).  Refused with PSG_ERR_INVALID before
+ * any device call: a null table, k outside [1, 16], iteration < 0, a null array
+ * where one is needed; with PSG_ERR_RANGE: sum(ns) > 2^32 - 2.  Every key of
+ * every frame is checked against the table's range before the first write: one
+ * key out of range fails the call with PSG_ERR_RANGE and rows, moments and size
+ * stay bit for bit unchanged.  Returns as psg_table_update: keys and gradients
+ * are no longer read, replies are in memory.  sum(ns) == 0 is a no-op.
+ * *path_host (may be NULL) says how the round was served: PSG_MERGED_SAME_LIST
+ * when all ns are equal, list 0 is strictly ascending and every list equals it
+ * element for element (the reference's own case, LRServer.h:145: no sort, list
+ * 0 resolved once), else PSG_MERGED_SORTED (the lists sorted as one, stably). */
+#define PSG_MERGED_SAME_LIST 1
+#define PSG_MERGED_SORTED 2
+int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys_host,
+                            const uint64_t* ns_host, const float* const* grads_host,
+                            float* const* outs_host, float lr, int iteration, psg_stream stream,
+                            int* path_host);
 /* The Adam moments in key order, info.size * width doubles each (whatever the
  * layout in HBM).  Fails with PSG_ERR_INVALID on a table without Adam state.
  * Synchronous. */

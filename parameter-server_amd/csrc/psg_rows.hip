@@ -41,6 +41,12 @@
 // it with one k_rows_move of `width` 16-B units through the same slot map.
 // Where width is a multiple of 4 each half is kept in the lane order of the
 // 16-B path (mom_col below).
+//
+// The merged update (psg_table_update_merged) is the sync-mode round
+// (LRServer.h:151-178) on rows: k gradient frames summed per key from zero in
+// arrival order, then one OptUnit::step per key.  Frames that all carry one
+// ascending list are served by k_rows_walk_same behind the strict front half;
+// anything else by the plan of the concatenated lists and k_rows_walk_merge.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -83,7 +89,8 @@ constexpr uint64_t kMaxRows = 0xfffffffeull;
 constexpr uint32_t kUnitsPerTile = 2048;
 constexpr int kUnroll = 4;  // loads a lane keeps in flight
 
-enum { R_MISSING = 0, R_RANGE = 1, R_UNSORTED = 2, kNFlags = 4 };
+// R_DIFFER: raised by k_keys_differ (psg_table_update_merged), after the resolve
+enum { R_MISSING = 0, R_RANGE = 1, R_UNSORTED = 2, R_DIFFER = 3, kNFlags = 4 };
 
 __device__ __forceinline__ void raise(int* flags, int which, bool cond) {
   if (__ballot(cond) && (threadIdx.x & 63) == 0) flags[which] = 1;
@@ -466,6 +473,178 @@ __global__ __launch_bounds__(256) void k_rows_walk_seg(typename UNIT::U* __restr
   }
 }
 
+// ---- the merged update (psg_table_update_merged) --------------------------------
+// k gradient frames, summed per key from +0.0f in arrival order (frame, then
+// position), then ONE step per key: the sync-mode round of LRServer.h:151-178 on
+// rows.  The frame table goes to the kernels by value.
+constexpr int kMaxFrames = 16;
+constexpr int kFrameGroup = 4;  // frames whose loads are issued before their ordered adds
+struct Frames {
+  // k_rows_walk_same: the frames' arrays.  k_rows_walk_merge: each moved back by
+  // its frame's off[j] rows, so that a position of the concatenation indexes it
+  const void* vals[kMaxFrames];
+  void* out[kMaxFrames];
+  uint32_t off[kMaxFrames + 1];  // first position of frame j in the concatenation; UINT32_MAX from k on
+  int k;
+};
+struct KeyFrames {
+  const uint64_t* p[kMaxFrames];
+  int k;
+};
+
+// Same-list test over the first n keys: every further key list equals list 0
+// element for element (8 B per key per further frame; a frame that IS list 0
+// is skipped); with `order`, list 0 also has to ascend strictly there.
+__global__ __launch_bounds__(256) void k_keys_differ(KeyFrames f, uint64_t n, int order, int* __restrict__ flags) {
+  int differ = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t x = f.p[0][i];
+    if (order && i > 0 && f.p[0][i - 1] >= x) differ = 1;
+    for (int j = 1; j < f.k; ++j)
+      if (f.p[j] != f.p[0] && f.p[j][i] != x) differ = 1;
+  }
+  raise(flags, R_DIFFER, differ != 0);
+}
+
+// Pass 2 of the same-list round: k_rows_walk's flat stream of units over the n
+// rows of list 0, every frame carrying its gradients of request row i at row i.
+// A unit's gradient is ((0 + f_0[ro]) + f_1[ro]) + ...: the loads of
+// kFrameGroup frames are issued before their adds, two units in flight.  Then
+// one step, one store, and the reply into every frame's out.
+template <typename UNIT, int OP>
+__global__ __launch_bounds__(256) void k_rows_walk_same(typename UNIT::U* __restrict__ R, double* __restrict__ M,
+                                                        const uint32_t* __restrict__ slots, Frames f, uint64_t n,
+                                                        uint32_t upr, uint32_t rpt, typename UNIT::Params prm) {
+  using U = typename UNIT::U;
+  constexpr int UN = 2;
+  const uint64_t ntiles = (n + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t i0 = t * rpt;
+    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += UN * kBlock) {
+      UNIT u[UN] = {};
+      U s[UN] = {};  // +0.0f: the merge buffer starts from zero
+      uint64_t ro[UN] = {};
+      bool ok[UN];
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t i = i0 + w.r;
+          u[k].locate(slots[i], w.c, upr, prm);
+          ro[k] = i * upr + w.c;
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < UN; ++k)
+        if (ok[k]) u[k].load_state(R, M, prm);
+      for (int j0 = 0; j0 < f.k; j0 += kFrameGroup) {
+        U g[UN][kFrameGroup];
+#pragma unroll
+        for (int j = 0; j < kFrameGroup; ++j)
+#pragma unroll
+          for (int k = 0; k < UN; ++k)
+            if (j0 + j < f.k && ok[k]) g[k][j] = UNIT::load_grad((const U*)f.vals[j0 + j], ro[k]);
+#pragma unroll
+        for (int j = 0; j < kFrameGroup; ++j)
+#pragma unroll
+          for (int k = 0; k < UN; ++k)
+            if (j0 + j < f.k && ok[k]) s[k] = s[k] + g[k][j];
+      }
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        if (!ok[k]) continue;
+        u[k].step(s[k], prm);
+        u[k].store_state(R, M, prm);
+        if constexpr ((OP & PSG_PULL) != 0)
+          for (int j = 0; j < f.k; ++j) u[k].reply((U*)f.out[j], ro[k]);
+      }
+    }
+  }
+}
+
+// the frame that holds position pos of the concatenation: the last j with
+// off[j] <= pos (an empty frame shares its offset with the next one).  The
+// offsets ascend and are the same for every lane (scalar registers), so j is
+// the count of off[1 .. 15] <= pos: 15 compares and no load on the lane's
+// perm -> gradient chain.
+__device__ __forceinline__ uint32_t frame_of(const Frames& f, uint32_t pos) {
+  uint32_t j = 0;
+#pragma unroll
+  for (int i = 1; i < kMaxFrames; ++i) j += f.off[i] <= pos ? 1u : 0u;
+  return j;
+}
+
+// Pass 2 of the general round.  Unique row u (slot slots[u]) for u < m; its
+// occurrences are positions perm[seg[u] .. seg[u + 1]) of the concatenated
+// frames, in arrival order (the sort is stable and positions ascend with frame,
+// then row).  The lanes walk the unique rows as k_rows_walk_seg does; a lane
+// sums its unit over the occurrences from zero (the position two ahead and the
+// values one ahead are loaded before the current add), then takes one step on
+// the row (and moments) and stores once.  The row's loads are issued in front
+// of the loop and used after it: a lane has one unit in flight, so their latency
+// runs beside the perm -> gradient chain instead of behind it.  For a Pull it walks the
+// segment again and stores the updated unit to every occurrence's reply.  One
+// writer per row, no atomics.  A frame's array is picked per lane, so a block
+// keeps the (moved-back) array addresses in LDS: one 8-B LDS read an occurrence.
+template <typename UNIT, int OP>
+__global__ __launch_bounds__(256) void k_rows_walk_merge(typename UNIT::U* __restrict__ R, double* __restrict__ M,
+                                                         const uint32_t* __restrict__ slots,
+                                                         const uint32_t* __restrict__ seg,
+                                                         const uint32_t* __restrict__ perm, Frames f, uint64_t m,
+                                                         uint32_t upr, uint32_t rpt, typename UNIT::Params prm) {
+  using U = typename UNIT::U;
+  __shared__ uint64_t vals_at[kMaxFrames], out_at[kMaxFrames];
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < kMaxFrames; ++j) vals_at[j] = (uint64_t)f.vals[j], out_at[j] = (uint64_t)f.out[j];
+  }
+  __syncthreads();
+  const uint64_t ntiles = (m + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t u0 = t * rpt;
+    const uint32_t nr = (uint32_t)(m - u0 < rpt ? m - u0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
+      const uint64_t u = u0 + w.r;
+      const uint32_t c = w.c;
+      const uint32_t slot = slots[u];
+      const uint32_t p0 = seg[u];
+      const uint32_t pe = seg[u + 1];  // > p0: every unique key has an occurrence
+      auto grad_at = [&](uint32_t pos) {
+        return UNIT::load_grad((const U*)vals_at[frame_of(f, pos)], (uint64_t)pos * upr + c);
+      };
+      UNIT x;
+      x.locate(slot, c, upr, prm);
+      x.load_state(R, M, prm);  // issued here, used after the sum
+      uint32_t i1 = p0 + 1 < pe ? perm[p0 + 1] : 0;
+      U v = grad_at(perm[p0]);
+      U s = {};  // +0.0f
+      for (uint32_t p = p0; p < pe; ++p) {
+        const uint32_t i2 = p + 2 < pe ? perm[p + 2] : 0;
+        U vn = v;
+        if (p + 1 < pe) vn = grad_at(i1);
+        s = s + v;
+        i1 = i2, v = vn;
+      }
+      x.step(s, prm);
+      x.store_state(R, M, prm);
+      if constexpr ((OP & PSG_PULL) != 0) {
+        uint32_t i0 = perm[p0];
+        for (uint32_t p = p0; p < pe; ++p) {
+          const uint32_t in = p + 1 < pe ? perm[p + 1] : 0;
+          x.reply((U*)out_at[frame_of(f, i0)], (uint64_t)i0 * upr + c);
+          i0 = in;
+        }
+      }
+    }
+  }
+}
+
 unsigned grid_for(uint64_t blocks) {
   const uint64_t cap = (uint64_t)max_stream_blocks();
   if (blocks > cap) blocks = cap;
@@ -645,13 +824,9 @@ struct AnyPlan {  // the request as unique rows: slots in t->slots[m]
   const uint32_t *seg, *perm;
 };
 
-// A list in range that is not strictly ascending: sort (key, position) stably,
-// cut the runs of equal keys, resolve the unique list as a strict request.
-int plan_any(psg_table* t, const uint64_t* keys, uint64_t n, AnyPlan* plan, hipStream_t st) {
-  AnyScratch a;
-  PSG_TRY(any_scratch(t, n, &a));
-  // the sort permutes its key buffer: a copy, the caller's keys are never written
-  PSG_HIP(hipMemcpyAsync(a.k0, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+// The n keys in a.k0, all in range: sort (key, position) stably, cut the runs
+// of equal keys, resolve the unique list as a strict request.
+int plan_scratch(psg_table* t, const AnyScratch& a, uint64_t n, AnyPlan* plan, hipStream_t st) {
   int res = 0;
   const int bits = std::max(1, bit_width(t->key_end - 1));  // every key is below key_end
   PSG_TRY(radix_sort_u64(a.k0, a.p0, n, bits, true, a.k1, a.p1, a.counts, st, &res));
@@ -669,6 +844,15 @@ int plan_any(psg_table* t, const uint64_t* keys, uint64_t n, AnyPlan* plan, hipS
   plan->seg = a.seg;
   plan->perm = res ? a.p1 : a.p0;
   return PSG_OK;
+}
+
+// A list in range that is not strictly ascending.
+int plan_any(psg_table* t, const uint64_t* keys, uint64_t n, AnyPlan* plan, hipStream_t st) {
+  AnyScratch a;
+  PSG_TRY(any_scratch(t, n, &a));
+  // the sort permutes its key buffer: a copy, the caller's keys are never written
+  PSG_HIP(hipMemcpyAsync(a.k0, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  return plan_scratch(t, a, n, plan, st);
 }
 
 // ---- pass 2: the dispatch -----------------------------------------------------------
@@ -791,6 +975,141 @@ int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const u
     PSG_TRY(accumulate(t, flags, p, vals, out, n, st));
   // complete on return: keys and vals no longer read, a Pull's reply in memory
   PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+// ---- the merged update: dispatch and body -----------------------------------------
+// The same-list walk over the n rows of list 0 (plan null), or the merge walk
+// over the plan's unique rows.
+template <typename UNIT, int OP>
+int launch_merged(psg_table* t, const AnyPlan* p, const Frames& f, uint64_t n, uint32_t upr,
+                  const typename UNIT::Params& prm, hipStream_t st) {
+  using U = typename UNIT::U;
+  const uint32_t rpt = rows_per_tile(upr);
+  const uint64_t rows = p ? p->m : n;
+  const unsigned g = grid_for((rows + rpt - 1) / rpt);
+  if (p)
+    k_rows_walk_merge<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, f, rows, upr, rpt,
+                                                       prm);
+  else
+    k_rows_walk_same<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, f, rows, upr, rpt, prm);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+template <bool ADAM>
+int merged_adam(psg_table* t, int op, bool vec, const AnyPlan* p, const Frames& f, uint64_t n, float lr, int iteration,
+                hipStream_t st) {
+  const typename OptUnit<ADAM, true>::Params prm = {t->width, lr, adam_args(t, iteration)};
+  if (vec)
+    return op == PSG_PUSH ? launch_merged<OptUnit<ADAM, true>, PSG_PUSH>(t, p, f, n, t->width / 4, prm, st)
+                          : launch_merged<OptUnit<ADAM, true>, PSG_PUSH | PSG_PULL>(t, p, f, n, t->width / 4, prm, st);
+  const typename OptUnit<ADAM, false>::Params prm1 = {t->width, lr, prm.a};
+  return op == PSG_PUSH ? launch_merged<OptUnit<ADAM, false>, PSG_PUSH>(t, p, f, n, t->width, prm1, st)
+                        : launch_merged<OptUnit<ADAM, false>, PSG_PUSH | PSG_PULL>(t, p, f, n, t->width, prm1, st);
+}
+
+// Are the further key lists, over their first n keys, element for element list
+// 0 (and, with `order`, does list 0 ascend strictly there)?  The answer is
+// t->flags_host[R_DIFFER], which the caller or the resolve before has cleared.
+int keys_differ(psg_table* t, int k, const uint64_t* const* keys, uint64_t n, bool order, hipStream_t st) {
+  KeyFrames kf = {};
+  kf.k = k;
+  bool any = order;
+  for (int j = 0; j < k; ++j) {
+    kf.p[j] = keys[j];
+    any = any || keys[j] != keys[0];
+  }
+  if (!any) return PSG_OK;
+  k_keys_differ<<<grid_for((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(kf, n, order ? 1 : 0, t->flags);
+  PSG_HIP(hipGetLastError());
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+int update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys, const uint64_t* ns,
+                  const float* const* grads, float* const* outs, float lr, int iteration, psg_stream stream,
+                  int* path_host) {
+  const char* name = "psg_table_update_merged";
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  PSG_REQUIRE(k >= 1 && k <= kMaxFrames, PSG_ERR_INVALID, "%s: %d frames outside [1, %d]", name, k, kMaxFrames);
+  PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
+              "%s: flags %d are neither PUSH nor PUSH|PULL", name, flags);
+  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
+  PSG_REQUIRE(keys && ns && grads, PSG_ERR_INVALID, "%s: null keys, ns or grads array", name);
+  PSG_REQUIRE(!(flags & PSG_PULL) || outs, PSG_ERR_INVALID, "%s: pull without outs array", name);
+  const bool pull = (flags & PSG_PULL) != 0;
+  Frames f = {};
+  f.k = k;
+  uint64_t N = 0;
+  bool same = true;
+  bool vec = t->width % 4 == 0;
+  for (int j = 0; j < k; ++j) {
+    PSG_REQUIRE(ns[j] <= kMaxRows && N + ns[j] <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one round",
+                name);
+    f.off[j] = (uint32_t)N;
+    N += ns[j];
+    same = same && ns[j] == ns[0];
+    if (ns[j] == 0) continue;
+    PSG_REQUIRE(keys[j] && grads[j], PSG_ERR_INVALID, "%s: null keys or grads of frame %d", name, j);
+    PSG_REQUIRE(!pull || outs[j], PSG_ERR_INVALID, "%s: pull without out buffer of frame %d", name, j);
+    f.vals[j] = grads[j];
+    f.out[j] = pull ? outs[j] : nullptr;
+    vec = vec && aligned16(grads[j]) && (!pull || aligned16(outs[j]));  // optimize_vec's condition, every frame
+  }
+  for (int j = k; j <= kMaxFrames; ++j) f.off[j] = 0xffffffffu;
+  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
+  if (path_host) *path_host = 0;
+  if (N == 0) return PSG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // the same-list round: equal counts, list 0 strictly ascending, every list equal to it
+  const uint64_t n = ns[0];
+  if (same && k > 1) {
+    // the head of the lists first, one block: shuffled or differing lists are
+    // told apart here, for one small launch instead of a resolve of list 0
+    memset(t->flags_host, 0, kNFlags * sizeof(int));
+    PSG_TRY(keys_differ(t, k, keys, std::min<uint64_t>(n, kRowTile), true, st));
+    same = !t->flags_host[R_DIFFER];
+  }
+  bool resolved = false;  // t->flags_host holds the flags of the whole round's keys
+  if (same) {
+    PSG_TRY(resolve_first(t, keys[0], n, st));
+    resolved = k == 1;  // list 0 is the concatenation
+    same = !t->flags_host[R_UNSORTED];
+  }
+  if (same) {
+    PSG_TRY(require_in_range(t));
+    PSG_TRY(keys_differ(t, k, keys, n, false, st));
+    same = !t->flags_host[R_DIFFER];
+  }
+  AnyPlan plan;
+  const AnyPlan* p = nullptr;
+  if (same) {
+    PSG_TRY(resolve_finish(t, keys[0], n, st));
+  } else {
+    // the k lists one behind the other in the sort's key buffer; every key is
+    // checked against the range before the sort (and before the first write)
+    AnyScratch a;
+    PSG_TRY(any_scratch(t, N, &a));
+    for (int j = 0; j < k; ++j)
+      if (ns[j])
+        PSG_HIP(hipMemcpyAsync(a.k0 + f.off[j], keys[j], ns[j] * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    if (!resolved) PSG_TRY(resolve_first(t, a.k0, N, st));
+    PSG_TRY(require_in_range(t));
+    PSG_TRY(plan_scratch(t, a, N, &plan, st));
+    p = &plan;
+    // a position of the concatenation indexes a frame's arrays moved back by its offset
+    const uint64_t row_bytes = (uint64_t)t->width * sizeof(float);
+    for (int j = 0; j < k; ++j) {
+      if (f.vals[j]) f.vals[j] = (const void*)((uintptr_t)f.vals[j] - f.off[j] * row_bytes);
+      if (f.out[j]) f.out[j] = (void*)((uintptr_t)f.out[j] - f.off[j] * row_bytes);
+    }
+  }
+  PSG_TRY(t->adam ? merged_adam<true>(t, flags, vec, p, f, n, lr, iteration, st)
+                  : merged_adam<false>(t, flags, vec, p, f, n, lr, iteration, st));
+  // complete on return: keys and grads no longer read, the replies in memory
+  PSG_HIP(hipStreamSynchronize(st));
+  if (path_host) *path_host = same ? PSG_MERGED_SAME_LIST : PSG_MERGED_SORTED;
   return PSG_OK;
 }
 
@@ -924,6 +1243,12 @@ int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float*
 int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const float* grads, float* out, uint64_t n,
                          float lr, int iteration, psg_stream stream) {
   return serve("psg_table_update_any", true, true, t, flags, keys, grads, out, n, lr, iteration, stream);
+}
+
+int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys_host, const uint64_t* ns_host,
+                            const float* const* grads_host, float* const* outs_host, float lr, int iteration,
+                            psg_stream stream, int* path_host) {
+  return update_merged(t, flags, k, keys_host, ns_host, grads_host, outs_host, lr, iteration, stream, path_host);
 }
 
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {

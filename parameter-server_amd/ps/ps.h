@@ -10,6 +10,7 @@
 #include "ps/kv_app.h"
 #include "ps/row_handle.h"
 #include "ps/row_opt_handle.h"
+#include "ps/row_sync_handle.h"
 #include "ps/simple_app.h"
 
 namespace ps {

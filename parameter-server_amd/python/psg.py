@@ -27,6 +27,7 @@ F32, F64, F16, BF16 = 0, 1, 2, 3
 DENSE, SORTED = 0, 1
 PUSH, PULL = 1, 2
 RUN_ONE_BY_ONE, RUN_SAME_LIST, RUN_STRIDED = 0, 1, 2
+MERGED_SAME_LIST, MERGED_SORTED = 1, 2
 H2D, D2H, D2D = 0, 1, 2
 
 _NP = {F32: np.float32, F64: np.float64, F16: np.float16, BF16: np.uint16}
@@ -49,7 +50,7 @@ EXPORTS = [
     "psg_store_run_status", "psg_store_set_key_range",
     "psg_table_create", "psg_table_destroy", "psg_table_get_info", "psg_table_clear", "psg_table_handle",
     "psg_table_dump", "psg_table_set_adam", "psg_table_update", "psg_table_dump_moments",
-    "psg_table_handle_any", "psg_table_update_any",
+    "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
     "psg_comm_push_pull", "psg_comm_push_keyed", "psg_comm_pull_keyed",
@@ -158,6 +159,7 @@ def lib() -> C.CDLL:
             "psg_table_dump_moments": ([vp, vp, vp], i32),
             "psg_table_handle_any": ([vp, i32, vp, vp, vp, u64, vp], i32),
             "psg_table_update_any": ([vp, i32, vp, vp, vp, u64, f32, i32, vp], i32),
+            "psg_table_update_merged": ([vp, i32, i32, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -558,6 +560,21 @@ class Table:
         (psg_table_update_any): every occurrence is applied in arrival order."""
         _call("psg_table_update_any", self.h, flags, _ptr(keys), _ptr(grads), _ptr(out), n, lr, iteration,
               _s(stream))
+
+    def update_merged(self, flags: int, keys_list, grads_list, outs_list, ns, lr: float, iteration: int,
+                      stream=None) -> int:
+        """One sync-mode round (psg_table_update_merged): the gradients of the
+        len(ns) frames are summed per key from zero in arrival order, then one
+        optimizer step per key; with PULL every occurrence is answered with the
+        updated row.  keys_list[j] / grads_list[j] / outs_list[j] are device
+        arrays of ns[j] keys / rows (None for an empty frame; outs_list may be
+        None for a Push).  Returns MERGED_SAME_LIST or MERGED_SORTED."""
+        k = len(ns)
+        arr = lambda xs: None if xs is None else (C.c_void_p * k)(*[_ptr(x) for x in xs])
+        path = C.c_int(0)
+        _call("psg_table_update_merged", self.h, flags, k, arr(keys_list), (C.c_uint64 * k)(*ns), arr(grads_list),
+              arr(outs_list), lr, iteration, _s(stream), C.byref(path))
+        return path.value
 
     def dump_moments(self):
         """(m, v), each shaped (size, width), in key order."""
