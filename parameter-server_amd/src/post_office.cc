@@ -8,7 +8,10 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <iostream>
 #include <memory>
+#include <streambuf>
+#include <string>
 #include <thread>
 
 #include "internal/Env.h"
@@ -344,10 +347,70 @@ void PostOffice::Barrier(int customer_id, int node_group) {
 }
 
 // ---------------------------------------------------------------------------
+// Whole lines on stdout.  In a job of processes every node has a stdout of its
+// own; here the nodes are threads that share std::cout, and two workers' `cout
+// << "got error value: " << a << ", " << b << '\n'` would interleave piece by
+// piece ("0, 00, 0").  While the cluster runs, cout writes into a buffer per
+// thread that is handed on at a newline, at a flush and when the thread ends,
+// so a node's line stays whole.  No put area: every character comes through
+// xsputn / overflow, which touch only the caller's buffer and the locked sink.
+namespace {
+class LineBuf : public std::streambuf {
+ public:
+  explicit LineBuf(std::streambuf* sink) : sink_(sink) {}
+
+ protected:
+  int_type overflow(int_type ch) override {
+    if (traits_type::eq_int_type(ch, traits_type::eof())) return traits_type::not_eof(ch);
+    const char c = traits_type::to_char_type(ch);
+    xsputn(&c, 1);
+    return ch;
+  }
+  std::streamsize xsputn(const char* p, std::streamsize n) override {
+    std::string& s = Mine();
+    s.append(p, (size_t)n);
+    const size_t nl = s.rfind('\n');
+    if (nl != std::string::npos) Emit(s, nl + 1);
+    return n;
+  }
+  int sync() override {
+    std::string& s = Mine();
+    Emit(s, s.size());
+    std::lock_guard<std::mutex> lk(mu_);
+    return sink_->pubsync();
+  }
+
+ private:
+  struct Pending {  // a thread's unfinished line; what is left goes out when the thread ends
+    LineBuf* owner = nullptr;
+    std::string s;
+    ~Pending() {
+      if (owner) owner->Emit(s, s.size());
+    }
+  };
+  std::string& Mine() {
+    thread_local Pending p;
+    p.owner = this;
+    return p.s;
+  }
+  void Emit(std::string& s, size_t n) {
+    if (n == 0) return;
+    std::lock_guard<std::mutex> lk(mu_);
+    sink_->sputn(s.data(), (std::streamsize)n);
+    s.erase(0, n);
+  }
+  std::streambuf* const sink_;
+  std::mutex mu_;
+};
+}  // namespace
+
 int RunLocalCluster(int num_servers, int num_workers, const std::function<int(int, char**)>& node_main,
                     int argc, char** argv) {
   CHECK_GT(num_servers, 0);
   CHECK_GT(num_workers, 0);
+  // never destroyed: a thread that ends late still finds it
+  static LineBuf* const lines = new LineBuf(std::cout.rdbuf());
+  std::streambuf* const cout_buf = std::cout.rdbuf(lines);
   ClusterState& s = S();
   {
     std::lock_guard<std::mutex> lk(s.mu);
@@ -442,6 +505,8 @@ int RunLocalCluster(int num_servers, int num_workers, const std::function<int(in
     for (auto& r : runs) std::remove(r->args[2].c_str());
     rmdir(dir.c_str());
   }
+  std::cout.flush();  // this thread's unfinished line
+  std::cout.rdbuf(cout_buf);
   std::lock_guard<std::mutex> lk(s.mu);
   s.configured = false;
   return rc;
