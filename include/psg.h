@@ -27,6 +27,9 @@
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
  *   psg_slice        KVWorker<V>::DefaultSlicer           src/ps/KVApp.h:515-574
  *   psg_merge        the AddPullCB merge lambda           src/ps/KVApp.h:673-726
+ *   psg_route / psg_rows_gather / psg_rows_scatter
+ *                    DefaultSlicer for a list in any order and with repeats
+ *                                                        src/ps/KVApp.h:515-574
  *   psg_comm_*       the ZMQ data path of Van::Send / ZMQVan::SendMsg / ReceiveMsg
  *                    (src/internal/Van.cpp:170-179, src/internal/ZMQVan.cpp:147-248)
  *                    for the BSP case: Push = reduce-scatter + accumulate,
@@ -621,6 +624,55 @@ int psg_slice(const uint64_t* keys, uint64_t n, const int* lens, uint64_t num_va
  * its server's range, and that server refuses the request). */
 int psg_slice_hint(const uint64_t* keys, uint64_t n, int num_servers, uint64_t begin0, uint64_t* key_pos_host,
                    int* found);
+
+/* DefaultSlicer (KVApp.h:515-574) for a key list in ANY order and with repeats —
+ * the lists psg_table_handle_any / _update_any / _update_merged serve — which
+ * its lower_bounds cannot cut.  A key's owner is the server whose range holds
+ * it.  The routed form of keys[n] is its stable partition by owner: server 0's
+ * keys first, in their original relative order, then server 1's, and so on.
+ *   routed_keys[r] = keys[perm[r]]         perm[r]: the original position of
+ *                                          routed position r
+ *   key_pos[s] .. key_pos[s+1]             server s's stretch of routed_keys
+ * Every occurrence of a key has one owner and a server sees its keys in arrival
+ * order, so serving stretch s on server s with an any-order call and putting
+ * reply row r at original position perm[r] (psg_rows_scatter) gives, bit for
+ * bit, what one server over the whole range gives for the whole list.
+ * One stable counting pass whose digit is the owner.  A list whose owners never
+ * decrease — every sorted or non-descending list — is partitioned already:
+ * *identity_host = 1, key_pos is filled, and routed_keys and perm are NOT
+ * written (the caller sends its own arrays): 8 B read per key.  Otherwise
+ * *identity_host = 0 and 8 + 8 B are read, 8 + 4 written per key.
+ * 1 <= num_servers <= PSG_ROUTE_MAX_SERVERS; ranges contiguous, as psg_slice
+ * requires (the CHECK at KVApp.h:531); n <= 2^32 - 2; routed_keys (n keys) and
+ * perm (n words) are device arrays, needed whenever n > 0; key_pos_host holds
+ * ns + 1 entries.  Bad arguments fail with PSG_ERR_INVALID before any device
+ * call.  A key outside [begins[0], ends[ns-1]) fails the call with
+ * PSG_ERR_RANGE (the CHECK at KVApp.h:544; unlike psg_slice, a key below
+ * begins[0] is refused, not dropped).  n == 0: key_pos all zero, identity 1, no
+ * device call.  The caller's keys are never written.  Synchronises `stream`
+ * once, for the counts; the writes of routed_keys and perm are stream-ordered
+ * behind it.  Scratch is kept per thread and GPU, as psg_slice's: a steady
+ * caller allocates nothing, and calls of one thread use one stream. */
+#define PSG_ROUTE_MAX_SERVERS 64
+int psg_route(const uint64_t* keys, uint64_t n, int num_servers, const uint64_t* begins_host,
+              const uint64_t* ends_host, uint64_t* routed_keys, uint32_t* perm,
+              uint64_t* key_pos_host, int* identity_host, psg_stream stream);
+/* The value rows that go with a routed list (k = row_bytes / sizeof(V) values
+ * per key, the contract of KVApp.h:515-574), as raw bytes:
+ *   psg_rows_gather   dst row r       = src row perm[r]     for r < n
+ *   psg_rows_scatter  dst row perm[r] = src row r           for r < n
+ * gather puts a request's values into routed order; scatter puts the replies
+ * back at the caller's positions (scatter(gather(x)) == x).  perm is a
+ * permutation of [0, n), as psg_route writes it: every row has one writer.
+ * 1 <= row_bytes <= 4096 * 8; n <= 2^32 - 2; else PSG_ERR_INVALID, as for null
+ * rows or a null perm with n > 0, before any device call.  Rows move in 16-B
+ * vectors when row_bytes and both pointers allow, else in the widest of 8, 4, 2
+ * or 1 bytes that does.  Stream-ordered; 4 + 2 * row_bytes B of traffic a row.
+ * dst and src must not overlap.  n == 0 is a no-op. */
+int psg_rows_gather(void* dst, const void* src, const uint32_t* perm, uint64_t n,
+                    uint64_t row_bytes, psg_stream stream);
+int psg_rows_scatter(void* dst, const void* src, const uint32_t* perm, uint64_t n,
+                     uint64_t row_bytes, psg_stream stream);
 
 /* One pull reply (KVPairs from one server, KVApp.h:631-637). */
 typedef struct psg_segment {

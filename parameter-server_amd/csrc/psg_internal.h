@@ -124,7 +124,33 @@ int max_stream_blocks();
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ---- rows as a flat stream of units -------------------------------------------
+// vectors (or elements) one block of a row kernel (psg_rows.hip's walks and
+// moves, psg_route.hip's gather and scatter) serves per tile
+constexpr uint32_t kUnitsPerTile = 2048;
+constexpr int kUnroll = 4;  // loads a lane keeps in flight
+// rows per tile, so that a tile holds about kUnitsPerTile units (at least one row)
+inline uint32_t rows_per_tile(uint32_t upr) { return upr >= kUnitsPerTile ? 1u : kUnitsPerTile / upr; }
+
 #ifdef __HIPCC__
+// A lane's walk over a tile of rows as one flat stream of units (16-B vectors
+// or elements), `upr` units a row: unit e is column e % upr of row e / upr.
+// One division at the start, then steps of kBlock units.
+struct RowWalk {
+  uint32_t r, c, dr, dc, upr;
+  __device__ __forceinline__ RowWalk(uint32_t e, uint32_t units_per_row)
+      : r(e / units_per_row), c(e - r * units_per_row), dr(kBlock / units_per_row),
+        dc(kBlock - dr * units_per_row), upr(units_per_row) {}
+  __device__ __forceinline__ void next() {
+    r += dr;
+    c += dc;
+    if (c >= upr) {
+      c -= upr;
+      ++r;
+    }
+  }
+};
+
 // lower_bound by one wave: 64 lanes probe 64 evenly spaced keys per round and
 // a ballot brackets the answer, so a 10 M-key store takes 4 rounds of one
 // parallel load instead of 24 dependent loads.  Wave-uniform result.

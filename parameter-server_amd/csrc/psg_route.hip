@@ -1,0 +1,284 @@
+// psg_route.hip — worker-side routing of a key list in any order, with repeats,
+// to the servers that own its keys, and the row copies that go with it.
+//
+//   psg_route         the stable partition of keys[n] by owning server: what
+//                     DefaultSlicer's lower_bounds (src/ps/KVApp.h:515-574)
+//                     cannot give for a list that is not sorted
+//   psg_rows_gather   dst row r = src row perm[r]   (values into routed order)
+//   psg_rows_scatter  dst row perm[r] = src row r   (replies back to the caller's)
+//
+// Routing is ONE stable counting pass whose digit is the owner (psg_radix.h, the
+// machinery of psg_sort.hip's passes):
+//   k_route_hist  every key read once; its owner by a 6-step search over the
+//                 range ends in LDS; counts[owner][tile]; a flag when a key lies
+//                 outside the ranges, another when an owner is lower than its
+//                 predecessor's
+//   k_rs_scan     per owner, exclusive scan over the tiles; owner totals
+//   (host)        totals and flags read after one synchronisation: key_pos; a
+//                 list whose owners never decrease is already partitioned and
+//                 is left where it is
+//   k_rs_scatter  rank inside the tile by wave ballots and per-wave counts in
+//                 LDS, so arrival order is kept; writes routed_keys and perm
+// Bytes per key: 8 read for a list already partitioned, else 8 + 8 read and
+// 8 + 4 written.
+//
+// The two row copies walk the rows as one flat stream of units, as k_rows_walk
+// (psg_rows.hip) does, kUnroll loads a lane in flight.  perm is a permutation:
+// every row has one writer, no atomics.  Traffic: perm 4 B + 2 * row_bytes a row.
+#include <algorithm>
+#include <map>
+
+#include "psg_radix.h"
+
+namespace psg {
+
+namespace {
+
+constexpr int kMaxServers = PSG_ROUTE_MAX_SERVERS;
+constexpr uint64_t kMaxRouted = 0xfffffffeull;
+constexpr uint32_t kMaxRowBytes = 4096 * 8;
+
+struct Ends {
+  uint64_t v[kMaxServers];  // ends[0 .. ns-1) (the last end bounds no owner)
+};
+
+// The owner of a key as a digit: the number of range ends at or below it, at
+// most ns - 1 (a key at or above the last end is rejected by k_route_hist; here
+// it only has to stay inside the counters).
+struct OwnerDigit {
+  static constexpr int kBits = 6;
+  static_assert((1 << kBits) == kMaxServers, "a digit per server");
+  Ends e;
+  uint32_t nsm1;  // ns - 1
+  static __device__ __forceinline__ uint64_t* lds() {
+    __shared__ uint64_t s_ends[kMaxServers];
+    return s_ends;
+  }
+  __device__ __forceinline__ void prepare() const {
+    if (threadIdx.x < (unsigned)kMaxServers) lds()[threadIdx.x] = e.v[threadIdx.x];
+  }
+  __device__ __forceinline__ uint32_t operator()(uint64_t k) const {
+    const uint64_t* ends = lds();
+    uint32_t o = 0;
+#pragma unroll
+    for (uint32_t step = kMaxServers / 2; step; step >>= 1)
+      if (o + step <= nsm1 && ends[o + step - 1] <= k) o += step;
+    return o;
+  }
+};
+
+enum { F_RANGE = 0, F_ORDER = 1, kNFlags = 2 };
+
+// Pass 1.  counts[owner][tile]; flags[F_RANGE] when a key lies outside [lo, hi),
+// flags[F_ORDER] when some key's owner is lower than its predecessor's.  A wave
+// finds the lanes that share an owner with kBits ballots (as k_rs_scatter does)
+// and their first lane adds their number: a list that goes to two servers would
+// otherwise put 256 LDS atomics on two words.
+__global__ __launch_bounds__(kRsBlock) void k_route_hist(const uint64_t* __restrict__ keys, uint64_t n,
+                                                         OwnerDigit digit, uint64_t lo, uint64_t hi,
+                                                         uint32_t* __restrict__ counts, uint64_t ntiles,
+                                                         int* __restrict__ flags) {
+  __shared__ uint32_t h[kMaxServers];
+  const int tid = threadIdx.x, lane = tid & 63;
+  digit.prepare();
+  if (tid < kMaxServers) h[tid] = 0;
+  __syncthreads();
+  const uint64_t t0 = (uint64_t)blockIdx.x * kRsTile;
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  bool bad = false, desc = false;
+#pragma unroll 4
+  for (int r = 0; r < kRsRounds; ++r) {
+    const uint64_t i = t0 + (uint64_t)r * kRsBlock + tid;
+    const bool valid = i < n;
+    const uint64_t k = valid ? keys[i] : 0;
+    const uint32_t o = digit(k);
+    bad |= valid && (k < lo || k >= hi);
+    // the predecessor's owner: the lane below, or for a wave's first lane the
+    // key before it (a line the wave below has just read)
+    uint32_t prev = __shfl_up(o, 1, 64);
+    if (lane == 0) prev = (valid && i > 0) ? digit(keys[i - 1]) : o;
+    desc |= valid && o < prev;
+    uint64_t peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < OwnerDigit::kBits; ++b) {
+      const uint64_t bb = __ballot((o >> b) & 1u);
+      peers &= ((o >> b) & 1u) ? bb : ~bb;
+    }
+    if (valid && (peers & lt) == 0) atomicAdd(&h[o], (uint32_t)__popcll(peers));
+  }
+  if (__ballot(bad) && lane == 0) flags[F_RANGE] = 1;
+  if (__ballot(desc) && lane == 0) flags[F_ORDER] = 1;
+  __syncthreads();
+  if (tid < kMaxServers) counts[(uint64_t)tid * ntiles + blockIdx.x] = h[tid];
+}
+
+// dst row r = src row perm[r] (GATHER), or dst row perm[r] = src row r, for
+// r < n; rows of upr units of type U.  A position of perm outside [0, n) is
+// skipped: no row there to read or write.
+template <typename U, bool GATHER>
+__global__ __launch_bounds__(256) void k_rows_permute(U* __restrict__ dst, const U* __restrict__ src,
+                                                      const uint32_t* __restrict__ perm, uint64_t n, uint32_t upr,
+                                                      uint32_t rpt) {
+  constexpr int UN = kUnroll;
+  const uint64_t ntiles = (n + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t i0 = t * rpt;
+    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += UN * kBlock) {
+      uint64_t so[UN] = {}, to[UN] = {};
+      bool ok[UN];
+      U v[UN];
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t r = i0 + w.r;
+          const uint64_t p = perm[r];
+          ok[k] = p < n;
+          so[k] = (GATHER ? p : r) * upr + w.c;
+          to[k] = (GATHER ? r : p) * upr + w.c;
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < UN; ++k)
+        if (ok[k]) v[k] = src[so[k]];
+#pragma unroll
+      for (int k = 0; k < UN; ++k)
+        if (ok[k]) dst[to[k]] = v[k];
+    }
+  }
+}
+
+template <typename U, bool GATHER>
+int launch_permute(void* dst, const void* src, const uint32_t* perm, uint64_t n, uint32_t upr, hipStream_t st) {
+  const uint32_t rpt = rows_per_tile(upr);
+  uint64_t blocks = (n + rpt - 1) / rpt;
+  blocks = std::min<uint64_t>(blocks, (uint64_t)max_stream_blocks());
+  k_rows_permute<U, GATHER><<<(unsigned)blocks, kBlock, 0, st>>>((U*)dst, (const U*)src, perm, n, upr, rpt);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+// rows move as raw bytes, in the widest unit the row length and both pointers allow
+template <bool GATHER>
+int permute_rows(const char* name, void* dst, const void* src, const uint32_t* perm, uint64_t n, uint64_t row_bytes,
+                 hipStream_t st) {
+  PSG_REQUIRE(row_bytes >= 1 && row_bytes <= kMaxRowBytes, PSG_ERR_INVALID, "%s: row_bytes %llu outside [1, %u]", name,
+              (unsigned long long)row_bytes, kMaxRowBytes);
+  PSG_REQUIRE(n <= kMaxRouted, PSG_ERR_INVALID, "%s: %llu rows, more than 2^32-2", name, (unsigned long long)n);
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(dst && src, PSG_ERR_INVALID, "%s: null rows", name);
+  PSG_REQUIRE(perm, PSG_ERR_INVALID, "%s: null perm", name);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src) | (uintptr_t)row_bytes;
+  const uint32_t rb = (uint32_t)row_bytes;
+  if (a % 16 == 0) return launch_permute<u32x4, GATHER>(dst, src, perm, n, rb / 16, st);
+  if (a % 8 == 0) return launch_permute<uint64_t, GATHER>(dst, src, perm, n, rb / 8, st);
+  if (a % 4 == 0) return launch_permute<uint32_t, GATHER>(dst, src, perm, n, rb / 4, st);
+  if (a % 2 == 0) return launch_permute<uint16_t, GATHER>(dst, src, perm, n, rb / 2, st);
+  return launch_permute<uint8_t, GATHER>(dst, src, perm, n, rb, st);
+}
+
+// Per-thread, per-GPU scratch of the route, as the slicer's (psg_slice.hip):
+// the counters in HBM, grown on demand, and a pinned mirror of their tail, so a
+// steady caller allocates nothing.  Layout: counts[kMaxServers][ntiles], then
+// the kMaxServers owner totals, then the flags.
+constexpr int kTail = kMaxServers + kNFlags;
+struct RouteScratch {
+  uint32_t* counts = nullptr;
+  uint64_t cap = 0;  // words
+  uint32_t* tail_host = nullptr;
+};
+thread_local std::map<int, RouteScratch> t_route_scratch;
+
+int get_route_scratch(uint64_t words, RouteScratch** out) {
+  int dev = 0;
+  PSG_HIP(hipGetDevice(&dev));
+  RouteScratch& s = t_route_scratch[dev];
+  if (!s.tail_host) PSG_HIP(hipHostMalloc((void**)&s.tail_host, kTail * sizeof(uint32_t), hipHostMallocDefault));
+  if (s.cap < words) {
+    if (s.counts) PSG_HIP(hipFree(s.counts));
+    s.counts = nullptr;
+    s.cap = 0;
+    const uint64_t cap = std::max<uint64_t>(words * 2, 1 << 16);
+    PSG_HIP(hipMalloc((void**)&s.counts, cap * sizeof(uint32_t)));
+    s.cap = cap;
+  }
+  *out = &s;
+  return PSG_OK;
+}
+
+}  // namespace
+
+}  // namespace psg
+
+using namespace psg;
+
+extern "C" {
+
+int psg_route(const uint64_t* keys, uint64_t n, int num_servers, const uint64_t* begins_host,
+              const uint64_t* ends_host, uint64_t* routed_keys, uint32_t* perm, uint64_t* key_pos_host,
+              int* identity_host, psg_stream stream) {
+  PSG_REQUIRE(num_servers > 0 && num_servers <= kMaxServers, PSG_ERR_INVALID, "psg_route: %d servers outside [1, %d]",
+              num_servers, kMaxServers);
+  PSG_REQUIRE(begins_host && ends_host && key_pos_host && identity_host, PSG_ERR_INVALID,
+              "psg_route: null ranges or outputs");
+  for (int i = 0; i < num_servers; ++i) {
+    PSG_REQUIRE(begins_host[i] <= ends_host[i], PSG_ERR_INVALID, "psg_route: range %d ends before it begins", i);
+    PSG_REQUIRE(i == 0 || ends_host[i - 1] == begins_host[i], PSG_ERR_INVALID,
+                "psg_route: ranges %d and %d are not adjacent (CHECK_EQ, KVApp.h:531)", i - 1, i);
+  }
+  PSG_REQUIRE(n <= kMaxRouted, PSG_ERR_INVALID, "psg_route: %llu keys, more than 2^32-2", (unsigned long long)n);
+  if (n == 0) {
+    for (int i = 0; i <= num_servers; ++i) key_pos_host[i] = 0;
+    *identity_host = 1;
+    return PSG_OK;
+  }
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "psg_route: null keys");
+  PSG_REQUIRE(routed_keys && perm, PSG_ERR_INVALID, "psg_route: null routed_keys or perm");
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t ntiles = rs_tiles(n);
+  RouteScratch* sc = nullptr;
+  PSG_TRY(get_route_scratch(kMaxServers * ntiles + kTail, &sc));
+  uint32_t* counts = sc->counts;
+  uint32_t* dtot = counts + kMaxServers * ntiles;
+  int* flags = (int*)(dtot + kMaxServers);
+  OwnerDigit digit;
+  for (int i = 0; i < kMaxServers; ++i) digit.e.v[i] = i < num_servers - 1 ? ends_host[i] : UINT64_MAX;
+  digit.nsm1 = (uint32_t)(num_servers - 1);
+  PSG_HIP(hipMemsetAsync(flags, 0, kNFlags * sizeof(int), st));
+  k_route_hist<<<(unsigned)ntiles, kRsBlock, 0, st>>>(keys, n, digit, begins_host[0], ends_host[num_servers - 1],
+                                                      counts, ntiles, flags);
+  k_rs_scan<><<<kMaxServers, kRsBlock, 0, st>>>(counts, ntiles, dtot);
+  PSG_HIP(hipGetLastError());
+  PSG_HIP(hipMemcpyAsync(sc->tail_host, dtot, kTail * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  const uint32_t* tail = sc->tail_host;
+  if (tail[kMaxServers + F_RANGE]) {
+    set_error("psg_route: a key lies outside the server ranges [%llu, %llu) (KVApp.h:544)",
+              (unsigned long long)begins_host[0], (unsigned long long)ends_host[num_servers - 1]);
+    return PSG_ERR_RANGE;
+  }
+  key_pos_host[0] = 0;
+  for (int i = 0; i < num_servers; ++i) key_pos_host[i + 1] = key_pos_host[i] + tail[i];
+  *identity_host = tail[kMaxServers + F_ORDER] ? 0 : 1;
+  if (*identity_host) return PSG_OK;
+  k_rs_scatter<uint64_t, true><<<(unsigned)ntiles, kRsBlock, 0, st>>>(keys, nullptr, routed_keys, perm, n, digit, counts,
+                                                                     dtot, ntiles);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+int psg_rows_gather(void* dst, const void* src, const uint32_t* perm, uint64_t n, uint64_t row_bytes,
+                    psg_stream stream) {
+  return permute_rows<true>("psg_rows_gather", dst, src, perm, n, row_bytes, (hipStream_t)stream);
+}
+
+int psg_rows_scatter(void* dst, const void* src, const uint32_t* perm, uint64_t n, uint64_t row_bytes,
+                     psg_stream stream) {
+  return permute_rows<false>("psg_rows_scatter", dst, src, perm, n, row_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -85,9 +85,6 @@ namespace {
 constexpr int kRowTile = 1024;  // request keys per block of the resolve (4 per lane)
 constexpr uint32_t kAbsent = 0xffffffffu;
 constexpr uint64_t kMaxRows = 0xfffffffeull;
-// vectors (or elements) one block of k_rows_walk / k_rows_move serves per tile
-constexpr uint32_t kUnitsPerTile = 2048;
-constexpr int kUnroll = 4;  // loads a lane keeps in flight
 
 // R_DIFFER: raised by k_keys_differ (psg_table_update_merged), after the resolve
 enum { R_MISSING = 0, R_RANGE = 1, R_UNSORTED = 2, R_DIFFER = 3, kNFlags = 4 };
@@ -164,26 +161,8 @@ __global__ __launch_bounds__(256) void k_rows_merge_keys(const uint64_t* __restr
   }
 }
 
-// A lane's walk over a tile of rows as one flat stream of units (16-B vectors
-// or elements), `upr` units a row: unit e is column e % upr of row e / upr.
-// One division at the start, then steps of kBlock units.
-struct RowWalk {
-  uint32_t r, c, dr, dc, upr;
-  __device__ __forceinline__ RowWalk(uint32_t e, uint32_t units_per_row)
-      : r(e / units_per_row), c(e - r * units_per_row), dr(kBlock / units_per_row),
-        dc(kBlock - dr * units_per_row), upr(units_per_row) {}
-  __device__ __forceinline__ void next() {
-    r += dr;
-    c += dc;
-    if (c >= upr) {
-      c -= upr;
-      ++r;
-    }
-  }
-};
-
-// rows per tile, so that a tile holds about kUnitsPerTile units (at least one row)
-inline uint32_t rows_per_tile(uint32_t upr) { return upr >= kUnitsPerTile ? 1u : kUnitsPerTile / upr; }
+// (RowWalk, a lane's walk over a tile of rows as one flat stream of units, and
+// rows_per_tile are in psg_internal.h: psg_route.hip's kernels walk the same way)
 
 // Merge, rows: dst row to[j] = src row j (src == nullptr: a zero row), for j < nrows.
 template <typename U>

@@ -382,6 +382,68 @@ class KVWorker : public SimpleApp {
     return ts;
   }
 
+  /* ---- key lists in any order and with repeats ----------------------------------
+   * The calls above cut a request by lower_bound (DefaultSlicer, KVApp.h:515-574),
+   * which presumes ascending keys.  These six take a minibatch's id list as it
+   * is — any order, hot ids named many times — and route it: the list's stable
+   * partition by owning server (psg_route), so every server gets its keys in
+   * arrival order, and every reply row goes back to the position its key had
+   * in the caller's list.  With servers whose handle serves such lists (the row
+   * handles built with any_order, KVServerRowSyncHandle) the result is, bit for
+   * bit, that of one server over the whole key range serving the whole list.
+   * Arguments as the namesake's, without lens (rows have one width).  CHECKs:
+   * no custom slicer is installed (routing presumes range ownership); vals and
+   * the output hold a multiple of keys.size() values.
+   *
+   * Z forms: keys, vals and the output live in HBM.  One server: the list goes
+   * on whole, as ZPush / ZPull / ZPushPull send it.  A list already partitioned
+   * by owner (every sorted list) is sent from the caller's own arrays on the
+   * bounds psg_route returned — one extra pass over the keys, no copy.  Any
+   * other list: pooled HBM frames take the routed keys, perm and the gathered
+   * values (psg_rows_gather); each server is sent its stretch on psg_route's
+   * exact bounds (no slicer kernel, no hint, no unconfirmed slice); a Pull's
+   * replies land in a routed output frame, offered to the servers for direct
+   * reply as ZPull offers its output; when the last reply is in,
+   * psg_rows_scatter puts the rows at the caller's positions, the frames go
+   * back to the pool, and then the callback runs.  Wait(ts) returns after that. */
+  int ZPushAny(const SVector<Key>& keys, const SVector<Value>& vals, int cmd = 0, const Callback& cb = nullptr,
+               int priority = 0) {
+    return SendAny(keys, &vals, nullptr, cmd, cb, priority);
+  }
+  int ZPullAny(const SVector<Key>& keys, SVector<Value>* vals, int cmd = 0, const Callback& cb = nullptr,
+               int priority = 0) {
+    CHECK_NOTNULL(vals);
+    return SendAny(keys, nullptr, vals, cmd, cb, priority);
+  }
+  int ZPushPullAny(const SVector<Key>& keys, const SVector<Value>& vals, SVector<Value>* outs, int cmd = 0,
+                   const Callback& cb = nullptr, int priority = 0) {
+    CHECK_NOTNULL(outs);
+    CHECK_EQ(vals.size(), outs->size()) << "ZPushPullAny: the output mirrors vals";
+    return SendAny(keys, &vals, outs, cmd, cb, priority);
+  }
+  /* Host-vector forms: the same routing done on the host (a stable counting
+   * pass over the owners), the routed copies sent as host frames on its bounds,
+   * the replies un-permuted on the host in the callback.  A correctness path,
+   * not a fast one: every value is copied twice by one thread. */
+  int PushAny(const std::vector<Key>& keys, const std::vector<Value>& vals, int cmd = 0, const Callback& cb = nullptr,
+              int priority = 0) {
+    return SendAnyHost(keys, &vals, nullptr, cmd, cb, priority);
+  }
+  int PullAny(const std::vector<Key>& keys, std::vector<Value>* vals, int cmd = 0, const Callback& cb = nullptr,
+              int priority = 0) {
+    CHECK_NOTNULL(vals);
+    return SendAnyHost(keys, nullptr, vals, cmd, cb, priority);
+  }
+  int PushPullAny(const std::vector<Key>& keys, const std::vector<Value>& vals, std::vector<Value>* outs, int cmd = 0,
+                  const Callback& cb = nullptr, int priority = 0) {
+    CHECK_NOTNULL(outs);
+    if (outs->empty())
+      outs->resize(vals.size());
+    else
+      CHECK_EQ(vals.size(), outs->size());
+    return SendAnyHost(keys, &vals, outs, cmd, cb, priority);
+  }
+
   /* slices its servers refused (Refused; PS_SPEC_SLICE) */
   uint64_t refused_slices() const { return refused_.load(); }
   void set_slicer(const Slicer& slicer) {
@@ -451,12 +513,27 @@ class KVWorker : public SimpleApp {
   void RunCallback(int timestamp);
   void Send(int timestamp, bool push, bool pull, int cmd, const Data& kvs, bool direct = false,
             const SVector<Value>* outs = nullptr);
+  /* the slices of a request to their servers (Send, SendBounds) */
+  void SendSliced(int timestamp, bool push, bool pull, int cmd, const Data& kvs, SlicedKVs& sliced, bool direct,
+                  const SVector<Value>* outs, bool spec);
+  /* Send on key bounds known exactly (a routed list): pos[i] .. pos[i + 1] is
+   * server i's stretch.  No slicer, no hint, no unconfirmed slice. */
+  void SendBounds(int timestamp, bool push, bool pull, int cmd, const Data& kvs, const std::vector<uint64_t>& pos,
+                  bool direct, const SVector<Value>* outs);
+  /* the Z and host forms of the any-order calls: vals == nullptr: no Push,
+   * outs == nullptr: no Pull */
+  int SendAny(const SVector<Key>& keys, const SVector<Value>* vals, SVector<Value>* outs, int cmd, const Callback& cb,
+              int priority);
+  int SendAnyHost(const std::vector<Key>& keys, const std::vector<Value>* vals, std::vector<Value>* outs, int cmd,
+                  const Callback& cb, int priority);
   void OnReceive(const Message& msg) override;
   void DefaultSlicer(Data& send, const std::vector<Range>& ranges, SlicedKVs* sliced);
+  /* routed: the request went out on SendBounds — its keys are partitioned by
+   * owner, not sorted: replies are ordered by server, not looked up by key */
   template <typename C, typename D>
-  int AddPullCB(const SVector<Key>& keys, C* vals, D* lens, int cmd, const Callback& cb);
+  int AddPullCB(const SVector<Key>& keys, C* vals, D* lens, int cmd, const Callback& cb, bool routed = false);
   template <typename C, typename D>
-  void MergePull(const SVector<Key>& keys, std::vector<Reply>& kvs, C* vals, D* lens);
+  void MergePull(const SVector<Key>& keys, std::vector<Reply>& kvs, C* vals, D* lens, bool routed = false);
 
   std::unordered_map<int, std::vector<Reply>> recv_kvs_;
   std::unordered_map<int, Callback> callbacks_;
@@ -1341,6 +1418,12 @@ void KVWorker<Value>::Send(int timestamp, bool push, bool pull, int cmd, const D
     }
   }
   if (!spec) slicer_(const_cast<Data&>(kvs), ranges, &sliced);
+  SendSliced(timestamp, push, pull, cmd, kvs, sliced, direct, outs, spec);
+}
+
+template <typename Value>
+void KVWorker<Value>::SendSliced(int timestamp, bool push, bool pull, int cmd, const Data& kvs, SlicedKVs& sliced,
+                                 bool direct, const SVector<Value>* outs, bool spec) {
   int skipped = 0;
   for (auto& sl : sliced)
     if (!sl.first) ++skipped;
@@ -1350,6 +1433,195 @@ void KVWorker<Value>::Send(int timestamp, bool push, bool pull, int cmd, const D
     if (!sliced[i].first) continue;
     SendOne(timestamp, push, pull, cmd, kvs.priority, kvs, sliced[i].second, direct, outs, (int)i, spec);
   }
+}
+
+template <typename Value>
+void KVWorker<Value>::SendBounds(int timestamp, bool push, bool pull, int cmd, const Data& kvs,
+                                 const std::vector<uint64_t>& pos, bool direct, const SVector<Value>* outs) {
+  stage::Scope t_send(push ? "worker.send.push" : "worker.send.pull");
+  CHECK_GE(pos.size(), (size_t)2);
+  const size_t ns = pos.size() - 1;
+  const size_t nkeys = kvs.keys.size();
+  CHECK_EQ(pos[ns], nkeys);
+  const size_t per = nkeys ? kvs.vals.size() / nkeys : 0;
+  CHECK_EQ(per * nkeys, kvs.vals.size());
+  SlicedKVs sliced(ns);
+  for (size_t i = 0; i < ns; ++i) {
+    auto& sl = sliced[i];
+    sl.first = pos[i + 1] != pos[i];
+    if (!sl.first) continue;
+    sl.second.keys = kvs.keys.Slice(pos[i], pos[i + 1]);
+    sl.second.vals = kvs.vals.Slice(pos[i] * per, pos[i + 1] * per);
+  }
+  SendSliced(timestamp, push, pull, cmd, kvs, sliced, direct, outs, false);
+}
+
+// The Z forms of the any-order calls (see the class comment).  The frames of a
+// routed request — routed keys, perm, gathered values, the routed output — are
+// held by the completion's captures until it has run.
+template <typename Value>
+int KVWorker<Value>::SendAny(const SVector<Key>& keys, const SVector<Value>* vals, SVector<Value>* outs, int cmd,
+                             const Callback& cb, int priority) {
+  const bool push = vals != nullptr, pull = outs != nullptr;
+  CHECK(default_slicer_) << "an Any call routes by the servers' key ranges: it cannot be combined with a custom slicer";
+  CHECK(keys.empty() || keys.on_device()) << "the Z forms of the Any calls take keys in HBM (host keys: PushAny / "
+                                             "PullAny / PushPullAny)";
+  const size_t n = keys.size();
+  if (push) CHECK_EQ(n ? vals->size() / n * n : vals->size(), vals->size()) << "vals hold a whole number of rows";
+  if (pull) CHECK_EQ(n ? outs->size() / n * n : outs->size(), outs->size()) << "the output holds a whole number of rows";
+  const std::vector<Range>& ranges = PostOffice::Get()->GetServerRanges();
+  const size_t ns = ranges.size();
+  if (ns == 1 || n == 0) {  // the list goes on whole
+    if (push && pull) return ZPushPull(keys, *vals, outs, nullptr, cmd, cb, priority);
+    return push ? ZPush(keys, *vals, {}, cmd, cb, priority) : ZPull(keys, outs, nullptr, cmd, cb, priority);
+  }
+  if (push) CHECK(vals->on_device()) << "HBM keys need HBM values";
+  if (pull) CHECK(outs->on_device() && outs->size()) << "HBM keys need a sized HBM output";
+  const int dev = keys.device();
+  psg_stream st = device::ThreadStream();
+  std::vector<uint64_t> begins(ns), ends(ns), pos(ns + 1, 0);
+  for (size_t i = 0; i < ns; ++i) begins[i] = ranges[i].begin, ends[i] = ranges[i].end;
+  SVector<Key> rkeys = SVector<Key>::OnDevice(n, dev);
+  SVector<uint32_t> perm = SVector<uint32_t>::OnDevice(n, dev);
+  int identity = 0;
+  {
+    stage::Scope t("worker.route.device", n * sizeof(Key));
+    device::Check(psg_route(keys.data(), n, (int)ns, begins.data(), ends.data(), rkeys.data(), perm.data(), pos.data(),
+                            &identity, st),
+                  "psg_route");
+  }
+  Data kvs;
+  kvs.priority = priority;
+  const bool direct = pull && detail::DirectReplyOn();
+  if (identity) {
+    // already partitioned: the caller's own arrays on the route's bounds
+    kvs.keys = keys;
+    if (push) kvs.vals = *vals;
+    if (pull && !push && direct) kvs.vals = *outs;
+    const int ts = pull ? AddPullCB(keys, outs, (SVector<int>*)nullptr, cmd, cb, true) : customer_->NewRequest(kServerGroup);
+    if (!pull) AddCallback(ts, cb);
+    SendBounds(ts, push, pull, cmd, kvs, pos, direct, push && pull && direct ? outs : nullptr);
+    return ts;
+  }
+  kvs.keys = rkeys;
+  SVector<Value> rvals;
+  if (push) {
+    const size_t row = vals->size() / n * sizeof(Value);
+    rvals = SVector<Value>::OnDevice(vals->size(), dev);
+    stage::Scope t("worker.route.gather", 2 * vals->size() * sizeof(Value));
+    device::Check(psg_rows_gather(rvals.data(), vals->data(), perm.data(), n, row, st), "psg_rows_gather");
+    kvs.vals = rvals;
+  }
+  // the servers read the frames on streams of their own
+  device::Check(psg_stream_sync(st), "psg_stream_sync");
+  if (!pull) {
+    const int ts = customer_->NewRequest(kServerGroup);
+    AddCallback(ts, [rkeys, perm, rvals, cb]() {
+      if (cb) cb();
+    });
+    SendBounds(ts, true, false, cmd, kvs, pos, false, nullptr);
+    return ts;
+  }
+  auto routs = std::make_shared<SVector<Value>>(SVector<Value>::OnDevice(outs->size(), dev));
+  if (!push && direct) kvs.vals = *routs;
+  const SVector<Value> out = *outs;  // shares the caller's buffer
+  const int ts = AddPullCB(rkeys, routs.get(), (SVector<int>*)nullptr, cmd,
+                           [rkeys, perm, rvals, routs, out, n, cb]() mutable {
+                             const size_t row = out.size() / n * sizeof(Value);
+                             psg_stream s = device::ThreadStream();
+                             {
+                               stage::Scope t("worker.route.scatter", 2 * out.size() * sizeof(Value));
+                               device::Check(psg_rows_scatter(out.data(), routs->data(), perm.data(), n, row, s),
+                                             "psg_rows_scatter");
+                               device::Check(psg_stream_sync(s), "psg_stream_sync");
+                             }
+                             routs.reset();
+                             rkeys = SVector<Key>();
+                             perm = SVector<uint32_t>();
+                             rvals = SVector<Value>();
+                             if (cb) cb();
+                           },
+                           true);
+  SendBounds(ts, push, true, cmd, kvs, pos, direct, push && direct ? routs.get() : nullptr);
+  return ts;
+}
+
+// The host-vector forms: the same definition on the host.
+template <typename Value>
+int KVWorker<Value>::SendAnyHost(const std::vector<Key>& keys, const std::vector<Value>* vals,
+                                 std::vector<Value>* outs, int cmd, const Callback& cb, int priority) {
+  const bool push = vals != nullptr, pull = outs != nullptr;
+  CHECK(default_slicer_) << "an Any call routes by the servers' key ranges: it cannot be combined with a custom slicer";
+  const size_t n = keys.size();
+  if (n == 0) {
+    if (push && pull) return PushPull(keys, *vals, outs, nullptr, cmd, cb, priority);
+    return push ? Push(keys, *vals, {}, cmd, cb, priority) : Pull(keys, outs, nullptr, cmd, cb, priority);
+  }
+  if (push) CHECK_EQ(vals->size() / n * n, vals->size()) << "vals hold a whole number of rows";
+  if (pull) CHECK_EQ(outs->size() / n * n, outs->size()) << "the output holds a whole number of rows";
+  CHECK_LE(n, (size_t)0xfffffffeull);
+  const std::vector<Range>& ranges = PostOffice::Get()->GetServerRanges();
+  const size_t ns = ranges.size();
+  for (size_t i = 1; i < ns; ++i) CHECK_EQ(ranges[i - 1].end, ranges[i].begin);
+  // a stable counting pass whose digit is the owner
+  std::vector<uint32_t> owner(n);
+  std::vector<uint64_t> pos(ns + 1, 0);
+  bool identity = true;
+  for (size_t i = 0; i < n; ++i) {
+    const Key k = keys[i];
+    CHECK(k >= ranges[0].begin && k < ranges[ns - 1].end) << "key " << k << " lies outside the server ranges";
+    size_t o = 0;
+    while (k >= ranges[o].end) ++o;
+    owner[i] = (uint32_t)o;
+    ++pos[o + 1];
+    if (i && owner[i] < owner[i - 1]) identity = false;
+  }
+  for (size_t s = 0; s < ns; ++s) pos[s + 1] += pos[s];
+  auto perm = std::make_shared<std::vector<uint32_t>>();
+  Data kvs;
+  kvs.priority = priority;
+  if (identity) {
+    kvs.keys = SVector<Key>(keys);
+    if (push) kvs.vals = SVector<Value>(*vals);
+  } else {
+    perm->resize(n);
+    std::vector<uint64_t> at(pos.begin(), pos.end() - 1);
+    for (size_t i = 0; i < n; ++i) (*perm)[at[owner[i]]++] = (uint32_t)i;
+    kvs.keys = SVector<Key>::Uninitialized(n);
+    for (size_t r = 0; r < n; ++r) kvs.keys[r] = keys[(*perm)[r]];
+    if (push) {
+      const size_t per = vals->size() / n;
+      kvs.vals = SVector<Value>::Uninitialized(vals->size());
+      for (size_t r = 0; r < n; ++r)
+        std::memcpy(kvs.vals.data() + r * per, vals->data() + (size_t)(*perm)[r] * per, per * sizeof(Value));
+    }
+  }
+  if (!pull) {
+    const int ts = customer_->NewRequest(kServerGroup);
+    AddCallback(ts, cb);
+    SendBounds(ts, true, false, cmd, kvs, pos, false, nullptr);
+    return ts;
+  }
+  auto routs = std::make_shared<SVector<Value>>();
+  const int ts = AddPullCB(kvs.keys, routs.get(), (SVector<int>*)nullptr, cmd,
+                           [routs, perm, outs, n, identity, cb]() {
+                             if (outs->empty())
+                               outs->resize(routs->size());
+                             else
+                               CHECK_EQ(outs->size(), routs->size());
+                             const size_t per = routs->size() / n;
+                             if (identity) {
+                               std::memcpy(outs->data(), routs->data(), routs->size() * sizeof(Value));
+                             } else {
+                               for (size_t r = 0; r < n; ++r)
+                                 std::memcpy(outs->data() + (size_t)(*perm)[r] * per, routs->data() + r * per,
+                                             per * sizeof(Value));
+                             }
+                             if (cb) cb();
+                           },
+                           true);
+  SendBounds(ts, push, true, cmd, kvs, pos, false, nullptr);
+  return ts;
 }
 
 // One server's slice of a request (Send, SendPieces): `kv` is a slice of
@@ -1507,10 +1779,10 @@ void KVWorker<Value>::RunCallback(int timestamp) {
 
 template <typename Value>
 template <typename C, typename D>
-int KVWorker<Value>::AddPullCB(const SVector<Key>& keys, C* vals, D* lens, int cmd, const Callback& cb) {
+int KVWorker<Value>::AddPullCB(const SVector<Key>& keys, C* vals, D* lens, int cmd, const Callback& cb, bool routed) {
   (void)cmd;
   int ts = customer_->NewRequest(kServerGroup);
-  AddCallback(ts, [this, ts, keys, vals, lens, cb]() mutable {
+  AddCallback(ts, [this, ts, keys, vals, lens, cb, routed]() mutable {
     std::vector<Reply> kvs;
     {
       std::lock_guard<std::mutex> lk(mu_);
@@ -1520,7 +1792,7 @@ int KVWorker<Value>::AddPullCB(const SVector<Key>& keys, C* vals, D* lens, int c
         recv_kvs_.erase(it);
       }
     }
-    MergePull(keys, kvs, vals, lens);
+    MergePull(keys, kvs, vals, lens, routed);
     if (cb) cb();
   });
   return ts;
@@ -1528,13 +1800,13 @@ int KVWorker<Value>::AddPullCB(const SVector<Key>& keys, C* vals, D* lens, int c
 
 template <typename Value>
 template <typename C, typename D>
-void KVWorker<Value>::MergePull(const SVector<Key>& keys, std::vector<Reply>& kvs, C* vals, D* lens) {
+void KVWorker<Value>::MergePull(const SVector<Key>& keys, std::vector<Reply>& kvs, C* vals, D* lens, bool routed) {
   stage::Scope t_merge("worker.pull.merge", keys.size() * sizeof(Value));
   size_t total_key = 0, total_val = 0;
   int ndev = 0, ndirect = 0;
   for (const auto& r : kvs) {
     const auto& s = r.kv;
-    if (!s.keys.on_device() && !keys.on_device() && s.keys.size()) {
+    if (!routed && !s.keys.on_device() && !keys.on_device() && s.keys.size()) {
       Range range = FindRange(keys, s.keys.front(), s.keys.back() + 1);
       CHECK_EQ(range.size(), s.keys.size()) << "unmatched keys size from one server";
     }
@@ -1553,8 +1825,10 @@ void KVWorker<Value>::MergePull(const SVector<Key>& keys, std::vector<Reply>& kv
   CHECK_EQ(total_key, keys.size()) << "lost some servers?";
   CHECK(ndev == 0 || ndev + ndirect == (int)kvs.size()) << "pull replies mix host and HBM frames";
   // order the replies by their first key (KVApp.h:694-696); replies whose keys
-  // are in HBM are ordered by server rank, which the default ranges make the same
-  if (!keys.on_device()) {
+  // are in HBM, and those of a routed list (each server's stretch is in arrival
+  // order, not sorted), are ordered by server rank, which the default ranges
+  // make the same
+  if (!keys.on_device() && !routed) {
     std::sort(kvs.begin(), kvs.end(), [](const Reply& a, const Reply& b) {
       return a.kv.keys.front() < b.kv.keys.front();
     });

@@ -51,6 +51,7 @@ EXPORTS = [
     "psg_table_create", "psg_table_destroy", "psg_table_get_info", "psg_table_clear", "psg_table_handle",
     "psg_table_dump", "psg_table_set_adam", "psg_table_update", "psg_table_dump_moments",
     "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
+    "psg_route", "psg_rows_gather", "psg_rows_scatter",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
     "psg_comm_push_pull", "psg_comm_push_keyed", "psg_comm_pull_keyed",
@@ -163,6 +164,9 @@ def lib() -> C.CDLL:
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
+            "psg_route": ([vp, u64, i32, vp, vp, vp, vp, vp, C.POINTER(i32), vp], i32),
+            "psg_rows_gather": ([vp, vp, vp, u64, u64, vp], i32),
+            "psg_rows_scatter": ([vp, vp, vp, u64, u64, vp], i32),
             "psg_comm_id_bytes": ([], i32), "psg_comm_get_id": ([vp], i32),
             "psg_comm_bucket_plan": ([u64, i32, vp, vp, i32, C.POINTER(i32)], i32),
             "psg_comm_sync": ([vp, vp, f64], i32), "psg_comm_abort": ([vp], i32),
@@ -615,6 +619,33 @@ def slice_keys(keys, n: int, begins: np.ndarray, ends: np.ndarray, lens=None, nu
           begins.ctypes.data_as(C.c_void_p), ends.ctypes.data_as(C.c_void_p),
           kp.ctypes.data_as(C.c_void_p), vp.ctypes.data_as(C.c_void_p), _s(stream))
     return kp, vp
+
+
+ROUTE_MAX_SERVERS = 64
+
+
+def route(keys, n: int, begins: np.ndarray, ends: np.ndarray, routed_keys, perm, stream=None):
+    """The stable partition of a device key list by owning server (psg_route):
+    returns (key_pos[ns + 1], identity).  identity: the list was partitioned
+    already and routed_keys / perm were not written."""
+    ns = len(begins)
+    begins = np.ascontiguousarray(begins, dtype=np.uint64)
+    ends = np.ascontiguousarray(ends, dtype=np.uint64)
+    kp = np.empty(ns + 1, dtype=np.uint64)
+    ident = C.c_int(-1)
+    _call("psg_route", _ptr(keys), n, ns, begins.ctypes.data_as(C.c_void_p), ends.ctypes.data_as(C.c_void_p),
+          _ptr(routed_keys), _ptr(perm), kp.ctypes.data_as(C.c_void_p), C.byref(ident), _s(stream))
+    return kp, bool(ident.value)
+
+
+def rows_gather(dst, src, perm, n: int, row_bytes: int, stream=None) -> None:
+    """dst row r = src row perm[r] for r < n (stream-ordered)."""
+    _call("psg_rows_gather", _ptr(dst), _ptr(src), _ptr(perm), n, row_bytes, _s(stream))
+
+
+def rows_scatter(dst, src, perm, n: int, row_bytes: int, stream=None) -> None:
+    """dst row perm[r] = src row r for r < n (stream-ordered)."""
+    _call("psg_rows_scatter", _ptr(dst), _ptr(src), _ptr(perm), n, row_bytes, _s(stream))
 
 
 def merge(segments, elem_size: int, dst, dst_count: int, stream=None) -> None:
