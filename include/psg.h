@@ -590,6 +590,52 @@ int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* cons
  * layout in HBM).  Fails with PSG_ERR_INVALID on a table without Adam state.
  * Synchronous. */
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host);
+/* Whether the table has Adam state (*has_adam: 0 / 1) and, where params4 is not
+ * NULL, the four values psg_table_set_adam got: learning_rate, beta1, beta2,
+ * epsilon (zeros without Adam state).  Host only. */
+int psg_table_get_adam(psg_table* t, int* has_adam, double* params4);
+
+/* Put rows (and Adam moments) into the table as they are: the reading half of
+ * a saved model, lr::InitWeight with USE_OLD_MODEL (tests/src/LRServer.h:36-63:
+ * `input >> weight[i]` sets a weight, it does not add to it).  For i < n,
+ * j < width:
+ *   row(key_i)[j] = rows[i*width + j]                       -- AS BYTES
+ * Nothing is added and nothing is rounded: signed zeros, NaN payloads,
+ * signalling NaNs and subnormals of all four dtypes arrive unchanged (a Push
+ * into an empty table is 0 + x: it turns -0.0 into +0.0 and quiets NaNs).
+ * keys: n device keys, strictly ascending; rows: n * width elements of the
+ * table's dtype on the device.  An absent key is inserted once.
+ * m, v: device arrays of n * width doubles in plain column order (the order
+ * psg_table_dump_moments returns), both or neither:
+ *   both, Adam table:  the moments of the named rows become m and v;
+ *   neither:           a present key keeps its moments, an inserted key has
+ *                      zero moments (what USE_OLD_MODEL leaves of the
+ *                      reference's Adam: its m_ and v_ start from zero,
+ *                      Adam.h:40-41).
+ * Refused with PSG_ERR_INVALID before any device call, in this order: a null
+ * table; m without v or v without m; moments for a table without Adam state.
+ * Then the list is checked as psg_table_handle checks it, every key before the
+ * first write: out of order or repeated -> PSG_ERR_INVALID, a key outside the
+ * range -> PSG_ERR_RANGE, and keys, rows, moments and size stay bit for bit
+ * unchanged.  rows may be NULL (then m and v must be): the list's absent keys
+ * are inserted with zero rows and zero moments and nothing else is written, so
+ * a model that arrives in chunks costs one merge instead of one per chunk.
+ * Returns as psg_table_handle: keys, rows, m and v are no longer read.
+ * n == 0 is a no-op. */
+int psg_table_assign(psg_table* t, const uint64_t* keys, const void* rows, const double* m,
+                     const double* v, uint64_t n, psg_stream stream);
+/* The table's rows [first, first + count) in key order into DEVICE arrays: the
+ * writing half, lr::LRServer::SaveModel (tests/src/LRServer.h:107-115), as far
+ * as HBM.  keys_out (may be NULL): count keys; rows_out: count * width elements;
+ * m_out / v_out (both or neither, Adam tables only, else PSG_ERR_INVALID):
+ * count * width doubles each in plain column order.  first + count above the
+ * table's size fails with PSG_ERR_INVALID.  Host memory is never touched and
+ * the call is ordered on `stream`: the caller synchronises before it reads, and
+ * must not change the table before the copies have run.  So a checkpoint
+ * streams a table of any size through one bounded buffer, and a table moves
+ * into another (psg_table_assign) inside HBM.  count == 0 is a no-op. */
+int psg_table_export(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out,
+                     void* rows_out, double* m_out, double* v_out, psg_stream stream);
 
 /* ======================================================================== */
 /* Worker side: key-range slicing and pull merge                              */

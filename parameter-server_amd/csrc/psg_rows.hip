@@ -47,6 +47,13 @@
 // arrival order, then one OptUnit::step per key.  Frames that all carry one
 // ascending list are served by k_rows_walk_same behind the strict front half;
 // anything else by the plan of the concatenated lists and k_rows_walk_merge.
+//
+// Assign and export (psg_table_assign / psg_table_export) are the two halves of
+// a saved model (LRServer.h:36-63, 107-115).  Assign is a strict request on
+// SetUnit, which stores the request's row as bytes and never reads the old one;
+// export copies a stretch of K and R, which are in key order already.  The
+// moments go through k_mom_move in either direction, between the mom_col layout
+// and plain column order.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -227,6 +234,27 @@ template <int DT, bool VEC> struct AccUnit {
   __device__ __forceinline__ void reply(U* out, uint64_t ro) const { out[ro] = s; }
 };
 
+// Assign (psg_table_assign): row = the request's row, as bytes.  The unit is an
+// unsigned integer of the element's size or a 16-B vector of them, so no value
+// ever passes through a floating-point register class: signed zeros, NaN
+// payloads, signalling NaNs and subnormals arrive as they were sent.  The old
+// row is never read.  Algorithmic bytes per f32 key: key 8 + slot 8 + 8 * width.
+template <typename UU> struct SetUnit {
+  typedef UU U;
+  struct Params {};
+  static constexpr int kDepth = kUnroll;
+  uint64_t so;
+  U s;
+  __device__ __forceinline__ void locate(uint64_t slot, uint32_t c, uint32_t upr, const Params&) {
+    so = slot * upr + c;
+  }
+  __device__ __forceinline__ void load_state(const U*, const double*, const Params&) {}
+  __device__ static __forceinline__ U load_grad(const U* vals, uint64_t ro) { return vals[ro]; }
+  __device__ __forceinline__ void step(U v, const Params&) { s = v; }
+  __device__ __forceinline__ void store_state(U* R, double*, const Params&) const { R[so] = s; }
+  __device__ __forceinline__ void reply(U* out, uint64_t ro) const { out[ro] = s; }
+};
+
 // ---- the optimizer update ----------------------------------------------------
 // Where in its half (m or v) of a moment row the moment of column j lives.
 // width % 4 == 0: the unit of four columns 4u..4u+3 keeps the pair (4u, 4u+1)
@@ -383,6 +411,55 @@ __global__ __launch_bounds__(256) void k_rows_walk(typename UNIT::U* __restrict_
         }
         if constexpr ((OP & PSG_PULL) != 0) u[k].reply(out, ro[k]);
       }
+    }
+  }
+}
+
+// ---- the moments in and out (psg_table_assign / psg_table_export) ---------------
+// Request row i (slot slots[i], or first + i where slots is null) for i < n:
+// its moments between the table's moment row (mom_col layout) and the plain
+// arrays m, v of n * width doubles in column order.  TO_TABLE: plain -> table,
+// else table -> plain.  A unit is U: a pair of doubles (width % 4 == 0 and
+// m, v on 16 B) or one double; a moment row is 2 * width / E units, its m half
+// first.  Unit p of a half holds columns p * E .. and lives at mom_col(p * E):
+// mom_col keeps a pair of columns (2p, 2p + 1) together, so pairs of lanes
+// move 32 consecutive bytes on both sides.  kUnroll units in flight, every load
+// before the first store; one writer per unit, no atomics.
+template <typename U, bool TO_TABLE>
+__global__ __launch_bounds__(256) void k_mom_move(double* __restrict__ M, const uint32_t* __restrict__ slots,
+                                                  uint64_t first, double* __restrict__ m, double* __restrict__ v,
+                                                  uint64_t n, uint32_t width, uint32_t rpt) {
+  constexpr uint32_t E = sizeof(U) / sizeof(double);
+  const uint32_t uph = width / E;  // units per half
+  const uint32_t upr = 2 * uph;
+  const uint64_t ntiles = (n + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t i0 = t * rpt;
+    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += kUnroll * kBlock) {
+      U x[kUnroll];
+      U* dst[kUnroll] = {};
+      bool ok[kUnroll];
+#pragma unroll
+      for (int k = 0; k < kUnroll; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t i = i0 + w.r;
+          const uint64_t slot = slots ? (uint64_t)slots[i] : first + i;
+          const uint32_t h = w.c >= uph ? 1u : 0u;
+          const uint32_t j = (w.c - h * uph) * E;  // the unit's first column
+          U* tab = reinterpret_cast<U*>(M + slot * 2 * width + h * width + mom_col(j, width));
+          U* pln = reinterpret_cast<U*>((h ? v : m) + i * width + j);
+          x[k] = *(TO_TABLE ? pln : tab);
+          dst[k] = TO_TABLE ? tab : pln;
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < kUnroll; ++k)
+        if (ok[k]) *dst[k] = x[k];
     }
   }
 }
@@ -957,6 +1034,89 @@ int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const u
   return PSG_OK;
 }
 
+// ---- assign and export -----------------------------------------------------------
+// The moments of n request rows (slots: t->slots, or null for the table's rows
+// first .. first + n) between the table and the plain arrays m, v.
+template <bool TO_TABLE>
+int move_moments(psg_table* t, const uint32_t* slots, uint64_t first, const double* m, const double* v, uint64_t n,
+                 hipStream_t st) {
+  const bool pair = t->width % 4 == 0 && aligned16(m) && aligned16(v);
+  const uint32_t upr = pair ? t->width : 2 * t->width;
+  const uint32_t rpt = rows_per_tile(upr);
+  const unsigned g = grid_for((n + rpt - 1) / rpt);
+  double* mp = const_cast<double*>(m);
+  double* vp = const_cast<double*>(v);
+  if (pair)
+    k_mom_move<f64x2, TO_TABLE><<<g, kBlock, 0, st>>>(t->mom, slots, first, mp, vp, n, t->width, rpt);
+  else
+    k_mom_move<double, TO_TABLE><<<g, kBlock, 0, st>>>(t->mom, slots, first, mp, vp, n, t->width, rpt);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+template <typename U>
+int launch_set(psg_table* t, const void* rows, uint64_t n, uint32_t upr, hipStream_t st) {
+  const uint32_t rpt = rows_per_tile(upr);
+  k_rows_walk<SetUnit<U>, PSG_PUSH><<<grid_for((n + rpt - 1) / rpt), kBlock, 0, st>>>(
+      (U*)t->rows, nullptr, t->slots, (const U*)rows, nullptr, n, upr, rpt, typename SetUnit<U>::Params{});
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+int assign(psg_table* t, const uint64_t* keys, const void* rows, const double* m, const double* v, uint64_t n,
+           psg_stream stream) {
+  const char* name = "psg_table_assign";
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  PSG_REQUIRE((m != nullptr) == (v != nullptr), PSG_ERR_INVALID, "%s: m and v come as a pair, %s is null", name,
+              m ? "v" : "m");
+  PSG_REQUIRE(!m || t->adam, PSG_ERR_INVALID, "%s: moments for a table without Adam state", name);
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
+  PSG_REQUIRE(rows || !m, PSG_ERR_INVALID, "%s: moments without rows", name);
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(resolve_request(t, keys, n, st));
+  // no rows: the list's absent keys are in the table now (one merge for a whole
+  // model, where assigning it chunk by chunk would merge once per chunk)
+  if (!rows) return PSG_OK;
+  // 16-B units under accumulate_vec's condition for a Push
+  if (accumulate_vec(t, PSG_PUSH, rows, nullptr))
+    PSG_TRY(launch_set<u32x4>(t, rows, n, t->width * (uint32_t)t->esize / 16, st));
+  else if (t->esize == 8)
+    PSG_TRY(launch_set<uint64_t>(t, rows, n, t->width, st));
+  else if (t->esize == 4)
+    PSG_TRY(launch_set<uint32_t>(t, rows, n, t->width, st));
+  else
+    PSG_TRY(launch_set<uint16_t>(t, rows, n, t->width, st));
+  if (m) PSG_TRY(move_moments<true>(t, t->slots, 0, m, v, n, st));
+  // complete on return: keys, rows, m and v are no longer read
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+int export_rows(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out, void* rows_out, double* m_out,
+                double* v_out, psg_stream stream) {
+  const char* name = "psg_table_export";
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  PSG_REQUIRE((m_out != nullptr) == (v_out != nullptr), PSG_ERR_INVALID, "%s: m_out and v_out come as a pair, %s is null",
+              name, m_out ? "v_out" : "m_out");
+  PSG_REQUIRE(!m_out || t->adam, PSG_ERR_INVALID, "%s: moments of a table without Adam state", name);
+  PSG_REQUIRE(first <= t->size && count <= t->size - first, PSG_ERR_INVALID,
+              "%s: rows [%llu, %llu + %llu) of a table of %llu", name, (unsigned long long)first,
+              (unsigned long long)first, (unsigned long long)count, (unsigned long long)t->size);
+  if (count == 0) return PSG_OK;
+  PSG_REQUIRE(rows_out, PSG_ERR_INVALID, "%s: null rows_out", name);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t row_bytes = (uint64_t)t->width * t->esize;
+  // keys and rows are in key order in the table: two copies inside HBM
+  if (keys_out)
+    PSG_HIP(hipMemcpyAsync(keys_out, t->keys + first, count * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  PSG_HIP(hipMemcpyAsync(rows_out, (const char*)t->rows + first * row_bytes, count * row_bytes,
+                         hipMemcpyDeviceToDevice, st));
+  if (m_out) PSG_TRY(move_moments<false>(t, nullptr, first, m_out, v_out, count, st));
+  return PSG_OK;
+}
+
 // ---- the merged update: dispatch and body -----------------------------------------
 // The same-list walk over the n rows of list 0 (plan null), or the merge walk
 // over the plan's unique rows.
@@ -1228,6 +1388,23 @@ int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* cons
                             const float* const* grads_host, float* const* outs_host, float lr, int iteration,
                             psg_stream stream, int* path_host) {
   return update_merged(t, flags, k, keys_host, ns_host, grads_host, outs_host, lr, iteration, stream, path_host);
+}
+
+int psg_table_get_adam(psg_table* t, int* has_adam, double* params4) {
+  PSG_REQUIRE(t && has_adam, PSG_ERR_INVALID, "psg_table_get_adam: null argument");
+  *has_adam = t->adam;
+  if (params4) params4[0] = t->alr, params4[1] = t->beta1, params4[2] = t->beta2, params4[3] = t->eps;
+  return PSG_OK;
+}
+
+int psg_table_assign(psg_table* t, const uint64_t* keys, const void* rows, const double* m, const double* v,
+                     uint64_t n, psg_stream stream) {
+  return assign(t, keys, rows, m, v, n, stream);
+}
+
+int psg_table_export(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out, void* rows_out,
+                     double* m_out, double* v_out, psg_stream stream) {
+  return export_rows(t, first, count, keys_out, rows_out, m_out, v_out, stream);
 }
 
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {

@@ -11,7 +11,8 @@
 //   Pull:  res.vals[i * width + j] = row(key_i)[j]    (post-update)
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first
-// request; an absent key is inserted with a zero row.  By default keys must be
+// request (or by SaveModel / LoadModel, below); an absent key is inserted with
+// a zero row.  By default keys must be
 // strictly ascending (the KVPairs contract, KVApp.h:23): a list out of order or
 // with repeats fails the request's CHECK.  With any_order set the handle calls
 // psg_table_handle_any, which serves such a list in arrival order, every
@@ -21,12 +22,34 @@
 // their key lists for real.
 #pragma once
 #include <memory>
+#include <string>
 
 #include "ps/kv_app.h"
+#include "ps/row_checkpoint.h"
 
 namespace ps {
 
 namespace detail {
+
+// The row handles' table, created on first use (a request, SaveModel or
+// LoadModel): [0, kMaxKey), no rows allocated; with_adam gives it the moments
+// of Adam(learning_rate), as LRServer.h:83-84 constructs it.
+inline psg_table* EnsureRowTable(psg_table** table, int dtype, uint32_t width, bool with_adam = false,
+                                 float learning_rate = 0.f) {
+  if (*table) return *table;
+  device::Check(psg_table_create(dtype, width, 0, kMaxKey, 0, table), "psg_table_create");
+  if (with_adam) device::Check(psg_table_set_adam(*table, (double)learning_rate, 0.9, 0.999, 1e-8), "psg_table_set_adam");
+  return *table;
+}
+
+// LoadModel's body: the file's rows in this server's own key range
+// (PostOffice::GetServerRanges) into the table; the file's iteration count.
+inline int LoadOwnRows(psg_table* table, const std::string& path, int* iteration) {
+  PostOffice* po = PostOffice::Get();
+  CHECK(po->is_server()) << "LoadModel is called on a server node";
+  const Range& own = po->GetServerRanges()[po->my_rank()];
+  return LoadRowTable(table, path, own.begin, own.end, iteration);
+}
 
 // The body the row handles share.  Stages the request's keys and values into
 // HBM, takes the worker's own output slice or allocates the reply, runs
@@ -91,8 +114,7 @@ struct KVServerRowHandle {
     constexpr int dt = device::DType<Value>();
     CHECK_GE(dt, 0) << "KVServerRowHandle: value type not supported by the HBM table";
     CHECK(req_data.lens.empty()) << "KVServerRowHandle: rows have one fixed width, lens are not supported";
-    if (!state->table)
-      device::Check(psg_table_create(dt, state->width, 0, kMaxKey, 0, &state->table), "psg_table_create");
+    detail::EnsureRowTable(&state->table, dt, state->width);
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     if (req_meta.push) CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
     detail::ServeRows(req_meta, req_data, server, w,
@@ -105,6 +127,20 @@ struct KVServerRowHandle {
                           device::Check(psg_table_handle(state->table, flags, keys, vals, out, n, s),
                                         "psg_table_handle");
                       });
+  }
+
+  // The table to a file and back (ps/row_checkpoint.h; the reference's
+  // SaveModel / USE_OLD_MODEL, LRServer.h:107-115, 36-63).  Called on the server
+  // node between barriers, with no request in flight.  LoadModel assigns the
+  // keys of this server's own range and returns their number: call it once per
+  // saved shard, whatever the number of servers that saved.  An accumulate
+  // handle has no iteration: it saves 0.
+  void SaveModel(const std::string& path) {
+    SaveRowTable(detail::EnsureRowTable(&state->table, device::DType<Value>(), state->width), 0, path);
+  }
+  int LoadModel(const std::string& path) {
+    return detail::LoadOwnRows(detail::EnsureRowTable(&state->table, device::DType<Value>(), state->width), path,
+                               nullptr);
   }
 };
 

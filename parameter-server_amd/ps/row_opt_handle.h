@@ -16,7 +16,8 @@
 //                      moments are untouched.
 //   Pull:              res.vals[i * width + j] = row(key_i)[j].
 //
-// The rows live in a psg_table over [0, kMaxKey), created on the first request;
+// The rows live in a psg_table over [0, kMaxKey), created on the first request
+// (or by SaveModel / LoadModel, which write and read rows, moments and iteration);
 // an absent key starts from a zero row and zero moments.  Adam gets
 // ((double)learning_rate, 0.9, 0.999, 1e-8), as LRServer.h:83-84 constructs it.
 // The iteration is the server's one counter, as in the reference: there is no
@@ -27,6 +28,7 @@
 // KVServer::SetDeviceRequestHandle; host frames are staged into HBM.
 #pragma once
 #include <memory>
+#include <string>
 
 #include "ps/row_handle.h"
 
@@ -66,11 +68,7 @@ struct KVServerRowOptHandle {
     const int dev = PostOffice::Get()->device();
     CHECK_GE(dev, 0) << "KVServerRowOptHandle: the table lives in HBM and this node has no GPU";
     CHECK(req_data.lens.empty()) << "KVServerRowOptHandle: rows have one fixed width, lens are not supported";
-    if (!st.table) {
-      device::Check(psg_table_create(PSG_F32, st.width, 0, kMaxKey, 0, &st.table), "psg_table_create");
-      if (st.use_adam)
-        device::Check(psg_table_set_adam(st.table, (double)st.lr, 0.9, 0.999, 1e-8), "psg_table_set_adam");
-    }
+    Table();
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     const bool accumulate = req_meta.push && req_meta.cmd == kAccumulate;
     if (req_meta.push) {
@@ -96,6 +94,20 @@ struct KVServerRowOptHandle {
   }
 
   int iteration() const { return state->iteration; }
+
+  // Rows, moments and the iteration to a file and back (ps/row_checkpoint.h; the
+  // reference's SaveModel / USE_OLD_MODEL, LRServer.h:107-115, 36-63).  Called on
+  // the server node between barriers, with no request in flight.  LoadModel
+  // assigns the keys of this server's own range, SETS the iteration to the
+  // file's and returns the rows loaded: call it once per saved shard, whatever
+  // the number of servers that saved.
+  void SaveModel(const std::string& path) { SaveRowTable(Table(), state->iteration, path); }
+  int LoadModel(const std::string& path) { return detail::LoadOwnRows(Table(), path, &state->iteration); }
+
+ private:
+  psg_table* Table() {
+    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr);
+  }
 };
 
 }  // namespace ps

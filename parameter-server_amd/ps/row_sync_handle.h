@@ -32,12 +32,14 @@
 // Key lists may come in any order and repeat, inside a request and across the
 // round's requests.  A round merges at most 16 requests: more workers fail the
 // handle's CHECK.  The rows live in a psg_table over [0, kMaxKey), created on
-// the first request; an absent key starts from a zero row and zero moments.
+// the first request (or by SaveModel / LoadModel); an absent key starts from a
+// zero row and zero moments.
 // Adam gets ((double)learning_rate, 0.9, 0.999, 1e-8), as LRServer.h:83-84
 // constructs it.  Register with KVServer::SetDeviceRequestHandle; host frames
 // are staged into HBM.
 #pragma once
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "ps/row_handle.h"
@@ -89,11 +91,7 @@ struct KVServerRowSyncHandle {
     const int nw = PostOffice::Get()->num_workers();
     CHECK(nw <= kMaxWorkers) << "KVServerRowSyncHandle: a round merges at most " << kMaxWorkers << " workers, the job has "
                              << nw;
-    if (!st.table) {
-      device::Check(psg_table_create(PSG_F32, st.width, 0, kMaxKey, 0, &st.table), "psg_table_create");
-      if (st.use_adam)
-        device::Check(psg_table_set_adam(st.table, (double)st.lr, 0.9, 0.999, 1e-8), "psg_table_set_adam");
-    }
+    Table();
     if (req_meta.push) {
       CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
       CHECK(req_meta.cmd >= 0 && req_meta.cmd <= kAccumulate) << "KVServerRowSyncHandle: unknown Push cmd " << req_meta.cmd;
@@ -127,7 +125,23 @@ struct KVServerRowSyncHandle {
 
   int iteration() const { return state->iteration; }
 
+  // Rows, moments and the iteration to a file and back, as
+  // KVServerRowOptHandle::SaveModel / LoadModel; between rounds only: a round
+  // that is half gathered fails the CHECK.
+  void SaveModel(const std::string& path) {
+    CHECK(state->held.empty()) << "KVServerRowSyncHandle::SaveModel: " << state->held.size() << " Pushes of a round are held";
+    SaveRowTable(Table(), state->iteration, path);
+  }
+  int LoadModel(const std::string& path) {
+    CHECK(state->held.empty()) << "KVServerRowSyncHandle::LoadModel: " << state->held.size() << " Pushes of a round are held";
+    return detail::LoadOwnRows(Table(), path, &state->iteration);
+  }
+
  private:
+  psg_table* Table() {
+    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr);
+  }
+
   // LRServer.h:163-178: the update on the merged gradients, then every held answer
   static void Round(State& st, KVServer<float>* server) {
     const int k = (int)st.held.size();

@@ -51,6 +51,7 @@ EXPORTS = [
     "psg_table_create", "psg_table_destroy", "psg_table_get_info", "psg_table_clear", "psg_table_handle",
     "psg_table_dump", "psg_table_set_adam", "psg_table_update", "psg_table_dump_moments",
     "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
+    "psg_table_get_adam", "psg_table_assign", "psg_table_export",
     "psg_route", "psg_rows_gather", "psg_rows_scatter",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
@@ -161,6 +162,9 @@ def lib() -> C.CDLL:
             "psg_table_handle_any": ([vp, i32, vp, vp, vp, u64, vp], i32),
             "psg_table_update_any": ([vp, i32, vp, vp, vp, u64, f32, i32, vp], i32),
             "psg_table_update_merged": ([vp, i32, i32, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
+            "psg_table_get_adam": ([vp, C.POINTER(i32), C.POINTER(f64)], i32),
+            "psg_table_assign": ([vp, vp, vp, vp, vp, u64, vp], i32),
+            "psg_table_export": ([vp, u64, u64, vp, vp, vp, vp, vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -587,6 +591,24 @@ class Table:
         v = np.empty(i.size * self.width, dtype=np.float64)
         _call("psg_table_dump_moments", self.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p))
         return m.reshape(i.size, self.width), v.reshape(i.size, self.width)
+
+    def adam(self):
+        """None, or the (lr, beta1, beta2, eps) set_adam got."""
+        has, p = C.c_int(0), (C.c_double * 4)()
+        _call("psg_table_get_adam", self.h, C.byref(has), p)
+        return tuple(p) if has.value else None
+
+    def assign(self, keys, rows, n: int, m=None, v=None, stream=None) -> None:
+        """Set the rows of n ascending device keys to `rows` as bytes
+        (psg_table_assign); absent keys are inserted.  m / v (both or neither):
+        n * width doubles each in column order, the rows' Adam moments."""
+        _call("psg_table_assign", self.h, _ptr(keys), _ptr(rows), _ptr(m), _ptr(v), n, _s(stream))
+
+    def export(self, first: int, count: int, keys_out, rows_out, m_out=None, v_out=None, stream=None) -> None:
+        """Rows [first, first + count) in key order into device arrays
+        (psg_table_export); stream-ordered: synchronise before reading."""
+        _call("psg_table_export", self.h, first, count, _ptr(keys_out), _ptr(rows_out), _ptr(m_out), _ptr(v_out),
+              _s(stream))
 
     def close(self) -> None:
         if self.h.value:
