@@ -637,6 +637,42 @@ int psg_table_assign(psg_table* t, const uint64_t* keys, const void* rows, const
 int psg_table_export(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out,
                      void* rows_out, double* m_out, double* v_out, psg_stream stream);
 
+/* Read rows WITHOUT inserting: what an evaluation pass or a serving replica
+ * wants from ids it never trained.  keys: n device keys in ANY order and with
+ * repeats (a read has no order to keep, so nothing is sorted).  For every
+ * occurrence i < n:
+ *   key_i present:  out[i*width .. i*width + width) = the row AS BYTES (signed
+ *                   zeros and NaN payloads as they are stored), found[i] = 1;
+ *   otherwise:      the row is all zero bytes, found[i] = 0.
+ * out: n * width elements of the table's dtype on the device, or NULL
+ * (presence only); found: n device bytes, or NULL.  The table is unchanged:
+ * size, capacity, keys, rows and moments stay bit for bit and the device
+ * pointers of psg_table_info stay the same; nothing is allocated but request
+ * scratch.  Refused with PSG_ERR_INVALID before any device call, in this
+ * order: a null table; null keys; out and found both NULL (each with n > 0).
+ * A key outside [key_begin, key_end) fails the call with PSG_ERR_RANGE and
+ * neither out nor found is written.  The call is two kernels and ONE host
+ * synchronisation, at its end: the second kernel reads the first one's range
+ * flag on the device.  Returns as psg_table_handle: keys are no longer read,
+ * out and found are in memory.  n == 0 is a no-op. */
+int psg_table_lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* found, uint64_t n,
+                     psg_stream stream);
+/* Remove every key of the list that the table holds.  keys: n device keys in
+ * any order and with repeats; absent keys are ignored.  *erased_host (may be
+ * NULL) gets the number of rows removed.  The survivors keep their rows and
+ * moments bit for bit, in key order; an erased key that is named again later
+ * starts as any absent key does, from a zero row and zero moments.  Memory
+ * follows the rows: after a call that removed something capacity <=
+ * max(2 * size, 1024), and a table whose last key went holds no arrays, like a
+ * table created with capacity 0.  A call that removes nothing (n == 0, an
+ * empty table, no key of the list present) reallocates nothing and leaves the
+ * device pointers as they were.  A key outside the range fails the call with
+ * PSG_ERR_RANGE before anything changed.  The eviction policy is the
+ * caller's: this is the mechanism.  Returns once the table is in its new
+ * state; keys are no longer read. */
+int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* erased_host,
+                    psg_stream stream);
+
 /* ======================================================================== */
 /* Worker side: key-range slicing and pull merge                              */
 /* ======================================================================== */

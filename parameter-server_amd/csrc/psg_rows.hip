@@ -54,6 +54,15 @@
 // export copies a stretch of K and R, which are in key order already.  The
 // moments go through k_mom_move in either direction, between the mom_col layout
 // and plain column order.
+//
+// Lookup and erase (psg_table_lookup / psg_table_erase) are the two calls that
+// never insert: the reference's store[key] inserts on every access and never
+// erases (KVApp.h:446-454), which an evaluation pass or a table over a stream of
+// ids cannot live with.  Both resolve a list in any order without sorting it
+// (k_rows_resolve_any).  A lookup then reads on ReadUnit behind a flag on the
+// device (k_rows_read): two kernels, one synchronisation.  An erase marks the
+// named slots, compacts the survivors in order and gathers keys, rows and
+// moment rows into new arrays (k_rows_take): insert_missing backwards.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -84,6 +93,9 @@ struct psg_table {
   // buffers, perm, U and seg carved from one block grown on demand
   void* any_buf;
   uint64_t any_bytes;
+  // psg_table_lookup's flag words on the device (kNFlags ints, on first use):
+  // raised by its resolve and read by its walk, with no host in between
+  int* gate;
 };
 
 namespace psg {
@@ -146,6 +158,94 @@ __global__ __launch_bounds__(256) void k_rows_resolve(const uint64_t* __restrict
   raise(flags, R_UNSORTED, unsorted != 0);
 }
 
+// Pass 1 of the calls that never insert (psg_table_lookup, psg_table_erase):
+// the same tile and the same search for a list in ANY order.  The tile is
+// bracketed by its smallest and largest key (a wave reduction, then four words
+// of LDS) instead of its first and last, so an ascending list searches the
+// stretch k_rows_resolve searches and a shuffled one a wider, still correct
+// one.  Order is not looked at: only slots and R_RANGE are written.
+__global__ __launch_bounds__(256) void k_rows_resolve_any(const uint64_t* __restrict__ q, uint64_t n,
+                                                          const uint64_t* __restrict__ K, uint64_t S, uint64_t kb,
+                                                          uint64_t ke, uint32_t* __restrict__ slots,
+                                                          int* __restrict__ flags) {
+  constexpr int PER = kRowTile / kBlock;
+  __shared__ uint64_t wmin[kBlock / 64], wmax[kBlock / 64], win[2];
+  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int range = 0;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t t0 = t * kRowTile;
+    const uint64_t t1 = t0 + kRowTile < n ? t0 + kRowTile : n;
+    uint64_t key[PER];
+    uint64_t mn = ~0ull, mx = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const uint64_t i = t0 + (uint64_t)k * kBlock + threadIdx.x;
+      key[k] = i < t1 ? q[i] : 0;
+      if (i < t1) {
+        mn = key[k] < mn ? key[k] : mn;
+        mx = key[k] > mx ? key[k] : mx;
+      }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const uint64_t a = __shfl_xor(mn, d, 64), b = __shfl_xor(mx, d, 64);
+      mn = a < mn ? a : mn;
+      mx = b > mx ? b : mx;
+    }
+    if (lane == 0) wmin[w] = mn, wmax[w] = mx;
+    __syncthreads();
+    if (w < 2) {  // wave 0 brackets the tile's minimum, wave 1 its maximum
+      uint64_t x = w == 0 ? wmin[0] : wmax[0];
+#pragma unroll
+      for (int j = 1; j < kBlock / 64; ++j) {
+        if (w == 0) x = wmin[j] < x ? wmin[j] : x;
+        else x = wmax[j] > x ? wmax[j] : x;
+      }
+      uint64_t p = lower_bound_wave(K, S, x);
+      if (w == 1) p = p < S ? p + 1 : S;
+      if (lane == 0) win[w] = p;
+    }
+    __syncthreads();
+    const uint64_t lo = win[0];
+    const uint64_t hi = win[1] > lo ? win[1] : lo;
+    // lower_bound of the lane's PER keys in K[lo, hi) side by side: the stretch
+    // is the block's, so every search takes the same steps, and a step issues
+    // the PER probes before it uses one (a shuffled tile spans most of K, and
+    // one search at a time is a chain of ~23 dependent loads).  The answer is
+    // in [base, base + len]; a probe K[base + half] has base + half < hi <= S.
+    uint64_t base[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) base[k] = lo;
+    uint64_t len = hi - lo;
+    while (len > 1) {
+      const uint64_t half = len >> 1;
+      uint64_t probe[PER];
+#pragma unroll
+      for (int k = 0; k < PER; ++k) probe[k] = K[base[k] + half];
+#pragma unroll
+      for (int k = 0; k < PER; ++k) base[k] = probe[k] < key[k] ? base[k] + half : base[k];
+      len -= half;
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const uint64_t i = t0 + (uint64_t)k * kBlock + threadIdx.x;
+      if (i >= t1) continue;
+      if (key[k] < kb || key[k] >= ke) range = 1;
+      bool found = false;
+      uint64_t p = base[k];
+      if (len == 1) {  // lower_bound is p, or p + 1 where K[p] < key
+        const uint64_t x = K[p];
+        found = x == key[k];
+        if (x < key[k] && p + 1 < S) found = K[p + 1] == key[k], p = p + 1;
+      }
+      slots[i] = found ? (uint32_t)p : kAbsent;
+    }
+    __syncthreads();
+  }
+  raise(flags, R_RANGE, range != 0);
+}
+
 // Merge, keys: old row j goes to j + #(new keys < K[j]), new key t to
 // t + #(old keys < M[t]); the places are kept (old_to / new_to) for the rows.
 __global__ __launch_bounds__(256) void k_rows_merge_keys(const uint64_t* __restrict__ K, uint64_t S,
@@ -188,6 +288,49 @@ __global__ __launch_bounds__(256) void k_rows_move(const U* __restrict__ src, U*
       if (src) v = src[j * upr + w.c];
       dst[(uint64_t)to[j] * upr + w.c] = v;
     }
+  }
+}
+
+// The move the other way round (psg_table_erase): dst row j = src row from[j],
+// for j < nrows.  The writes are consecutive, the reads ascend with gaps.
+template <typename U>
+__global__ __launch_bounds__(256) void k_rows_take(const U* __restrict__ src, U* __restrict__ dst,
+                                                   const uint32_t* __restrict__ from, uint64_t nrows, uint32_t upr,
+                                                   uint32_t rpt) {
+  const uint64_t ntiles = (nrows + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t j0 = t * rpt;
+    const uint32_t nr = (uint32_t)(nrows - j0 < rpt ? nrows - j0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += kUnroll * kBlock) {
+      U x[kUnroll];
+      uint64_t d[kUnroll] = {};
+      bool ok[kUnroll];
+#pragma unroll
+      for (int k = 0; k < kUnroll; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t j = j0 + w.r;
+          x[k] = src[(uint64_t)from[j] * upr + w.c];
+          d[k] = j * upr + w.c;
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < kUnroll; ++k)
+        if (ok[k]) dst[d[k]] = x[k];
+    }
+  }
+}
+
+// The slots a list names, marked dead in an array over the table's S slots
+// (psg_table_erase); a slot named twice gets the same byte twice.
+__global__ __launch_bounds__(256) void k_mark_dead(const uint32_t* __restrict__ slots, uint64_t n,
+                                                   uint8_t* __restrict__ dead) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t s = slots[i];
+    if (s != kAbsent) dead[s] = 1;
   }
 }
 
@@ -252,6 +395,28 @@ template <typename UU> struct SetUnit {
   __device__ static __forceinline__ U load_grad(const U* vals, uint64_t ro) { return vals[ro]; }
   __device__ __forceinline__ void step(U v, const Params&) { s = v; }
   __device__ __forceinline__ void store_state(U* R, double*, const Params&) const { R[so] = s; }
+  __device__ __forceinline__ void reply(U* out, uint64_t ro) const { out[ro] = s; }
+};
+
+// Read (psg_table_lookup): the reply is the row as bytes, and a key the table
+// does not hold (slot kAbsent) answers with a zero row that is never loaded.
+// The unit is SetUnit's: an unsigned integer of the element's size or a 16-B
+// vector of them.  Nothing is stored to the table, so the unit has no step.
+// Algorithmic bytes per f32 key: key 8 + slot 8 + 8 * width (+ 1 for found).
+template <typename UU> struct ReadUnit {
+  typedef UU U;
+  static constexpr int kDepth = kUnroll;
+  uint64_t so;
+  bool present;
+  U s;
+  __device__ __forceinline__ void locate(uint32_t slot, uint32_t c, uint32_t upr) {
+    present = slot != kAbsent;
+    so = present ? (uint64_t)slot * upr + c : 0;
+  }
+  __device__ __forceinline__ void load_state(const U* R) {
+    s = U{};
+    if (present) s = R[so];
+  }
   __device__ __forceinline__ void reply(U* out, uint64_t ro) const { out[ro] = s; }
 };
 
@@ -415,6 +580,56 @@ __global__ __launch_bounds__(256) void k_rows_walk(typename UNIT::U* __restrict_
   }
 }
 
+// Pass 2 of psg_table_lookup: k_rows_walk's flat stream over the request's n
+// rows on ReadUnit, launched behind k_rows_resolve_any WITHOUT the host in
+// between.  What the host would have checked is checked here: `gate` is the
+// device word the resolve raised R_RANGE in, and a launch that finds it set
+// writes nothing.  An absent slot is allowed and loads nothing.  found[i] is
+// written by the lane that holds column 0 of row i: once per row.  out null:
+// presence only, one lane per row.
+template <typename U>
+__global__ __launch_bounds__(256) void k_rows_read(const U* __restrict__ R, const uint32_t* __restrict__ slots,
+                                                   U* __restrict__ out, uint8_t* __restrict__ found, uint64_t n,
+                                                   uint32_t upr, uint32_t rpt, const int* __restrict__ gate) {
+  using UNIT = ReadUnit<U>;
+  constexpr int UN = UNIT::kDepth;
+  if (gate[R_RANGE]) return;
+  if (!out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+      found[i] = slots[i] != kAbsent ? 1 : 0;
+    return;
+  }
+  const uint64_t ntiles = (n + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t i0 = t * rpt;
+    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += UN * kBlock) {
+      UNIT u[UN] = {};
+      uint64_t ro[UN] = {};  // the unit's offset in the reply
+      bool ok[UN];
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t i = i0 + w.r;
+          u[k].locate(slots[i], w.c, upr);
+          ro[k] = i * upr + w.c;
+          if (found && w.c == 0) found[i] = u[k].present ? 1 : 0;
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < UN; ++k)
+        if (ok[k]) u[k].load_state(R);
+#pragma unroll
+      for (int k = 0; k < UN; ++k)
+        if (ok[k]) u[k].reply(out, ro[k]);
+    }
+  }
+}
+
 // ---- the moments in and out (psg_table_assign / psg_table_export) ---------------
 // Request row i (slot slots[i], or first + i where slots is null) for i < n:
 // its moments between the table's moment row (mom_col layout) and the plain
@@ -479,6 +694,22 @@ struct EmitHead {
     seg[pos] = (uint32_t)i;
   }
   __device__ void done(uint32_t m) const { seg[m] = (uint32_t)n; }
+};
+
+// The survivors of an erase, in slot (= key) order: their keys and old slots.
+struct Alive {
+  const uint8_t* dead;
+  __device__ bool operator()(uint64_t i) const { return dead[i] == 0; }
+};
+struct EmitSurvivor {
+  const uint64_t* K;
+  uint64_t* K2;
+  uint32_t* from;
+  __device__ void operator()(uint64_t i, uint32_t pos) const {
+    K2[pos] = K[i];
+    from[pos] = (uint32_t)i;
+  }
+  __device__ void done(uint32_t) const {}
 };
 
 // Pass 2 of the any-order calls.  Unique row u (slot slots[u]) for u < m; its
@@ -1117,6 +1348,129 @@ int export_rows(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out
   return PSG_OK;
 }
 
+// ---- lookup and erase: the calls that never insert ---------------------------------
+template <typename U>
+int launch_read(psg_table* t, void* out, uint8_t* found, uint64_t n, uint32_t upr, hipStream_t st) {
+  const uint32_t rpt = rows_per_tile(upr);
+  const uint64_t blocks = out ? (n + rpt - 1) / rpt : (n + kBlock - 1) / kBlock;
+  k_rows_read<U><<<grid_for(blocks), kBlock, 0, st>>>((const U*)t->rows, t->slots, (U*)out, found, n, upr, rpt, t->gate);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+int lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* found, uint64_t n, psg_stream stream) {
+  const char* name = "psg_table_lookup";
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
+  PSG_REQUIRE(out || found, PSG_ERR_INVALID, "%s: out and found are both null", name);
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(ensure_slots(t, n));
+  if (!t->gate) PSG_HIP(hipMalloc((void**)&t->gate, kNFlags * sizeof(int)));
+  PSG_HIP(hipMemsetAsync(t->gate, 0, kNFlags * sizeof(int), st));
+  k_rows_resolve_any<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(keys, n, t->keys, t->size, t->key_begin,
+                                                                                  t->key_end, t->slots, t->gate);
+  PSG_HIP(hipGetLastError());
+  // 16-B units under accumulate_vec's condition for a Pull; presence alone has no unit
+  if (!out)
+    PSG_TRY(launch_read<u32x4>(t, nullptr, found, n, 1, st));
+  else if (accumulate_vec(t, PSG_PULL, nullptr, out))
+    PSG_TRY(launch_read<u32x4>(t, out, found, n, t->width * (uint32_t)t->esize / 16, st));
+  else if (t->esize == 8)
+    PSG_TRY(launch_read<uint64_t>(t, out, found, n, t->width, st));
+  else if (t->esize == 4)
+    PSG_TRY(launch_read<uint32_t>(t, out, found, n, t->width, st));
+  else
+    PSG_TRY(launch_read<uint16_t>(t, out, found, n, t->width, st));
+  // the one synchronisation: keys no longer read, the reply in memory, the flags on the host
+  PSG_HIP(hipMemcpyAsync(t->flags_host, t->gate, kNFlags * sizeof(int), hipMemcpyDeviceToHost, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  return require_in_range(t);
+}
+
+template <typename U>
+int launch_take(const void* src, void* dst, const uint32_t* from, uint64_t nrows, uint32_t upr, hipStream_t st) {
+  const uint32_t rpt = rows_per_tile(upr);
+  k_rows_take<U><<<grid_for((nrows + rpt - 1) / rpt), kBlock, 0, st>>>((const U*)src, (U*)dst, from, nrows, upr, rpt);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+// move_rows' units, gathered
+int take_rows(const psg_table* t, const void* src, void* dst, const uint32_t* from, uint64_t nrows, hipStream_t st) {
+  const uint32_t rb = t->width * (uint32_t)t->esize;
+  if (rb % 16 == 0) return launch_take<u32x4>(src, dst, from, nrows, rb / 16, st);
+  if (rb % 4 == 0) return launch_take<uint32_t>(src, dst, from, nrows, rb / 4, st);
+  return launch_take<uint16_t>(src, dst, from, nrows, rb / 2, st);
+}
+
+// insert_missing backwards: the slots the list names are marked dead, the
+// ordered compaction over the S slots gives the survivors' old slots, and keys,
+// rows and moment rows are gathered into new arrays that replace the old ones
+// after one synchronisation.
+int erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* erased_host, psg_stream stream) {
+  const char* name = "psg_table_erase";
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  if (erased_host) *erased_host = 0;
+  if (n == 0) return PSG_OK;
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(ensure_slots(t, n));
+  memset(t->flags_host, 0, kNFlags * sizeof(int));
+  k_rows_resolve_any<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(keys, n, t->keys, t->size, t->key_begin,
+                                                                                  t->key_end, t->slots, t->flags);
+  PSG_HIP(hipGetLastError());
+  PSG_HIP(hipStreamSynchronize(st));
+  PSG_TRY(require_in_range(t));
+  const uint64_t S = t->size;
+  if (S == 0) return PSG_OK;
+  const uint64_t ntiles = compact_tiles(S);
+  DevBuf dead, counts, from;
+  PSG_HIP(hipMalloc(&dead.p, S));
+  PSG_HIP(hipMalloc(&counts.p, (ntiles + 1) * sizeof(uint32_t)));
+  PSG_HIP(hipMemsetAsync(dead.p, 0, S, st));
+  k_mark_dead<<<grid_for((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(t->slots, n, (uint8_t*)dead.p);
+  const Alive alive = {(const uint8_t*)dead.p};
+  compact_count(S, (uint32_t*)counts.p, alive, st);
+  PSG_HIP(hipGetLastError());
+  uint64_t m = 0;  // the survivors
+  PSG_TRY(read_count((const uint32_t*)counts.p + ntiles, &m, st));
+  PSG_REQUIRE(m <= S, PSG_ERR_HIP, "%s: %llu survivors of %llu rows", name, (unsigned long long)m, (unsigned long long)S);
+  if (m == S) return PSG_OK;  // no key of the list is present
+  DevBuf K2, R2, M2;
+  uint64_t cap = 0;
+  if (m) {
+    cap = std::max<uint64_t>(m, 1024);
+    const uint64_t row_bytes = (uint64_t)t->width * t->esize;
+    PSG_HIP(hipMalloc(&from.p, m * sizeof(uint32_t)));
+    PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
+    PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
+    if (t->adam) PSG_HIP(hipMalloc(&M2.p, cap * mom_row_bytes(t)));
+    compact_emit(S, (const uint32_t*)counts.p, alive, EmitSurvivor{t->keys, (uint64_t*)K2.p, (uint32_t*)from.p}, st);
+    PSG_HIP(hipGetLastError());
+    PSG_TRY(take_rows(t, t->rows, R2.p, (const uint32_t*)from.p, m, st));
+    // a moment row is 2 * width doubles = width 16-B units, as insert_missing moves it
+    if (t->adam) PSG_TRY(launch_take<u32x4>(t->mom, M2.p, (const uint32_t*)from.p, m, t->width, st));
+    PSG_HIP(hipStreamSynchronize(st));
+  }
+  // the old arrays are freed with K2 / R2 / M2; a table whose last key went keeps none
+  void* old_keys = t->keys;
+  t->keys = (uint64_t*)K2.p;
+  K2.p = old_keys;
+  std::swap(R2.p, t->rows);
+  if (t->adam) {
+    void* old_mom = t->mom;
+    t->mom = (double*)M2.p;
+    M2.p = old_mom;
+  }
+  t->size = m;
+  t->capacity = cap;
+  if (erased_host) *erased_host = S - m;
+  return PSG_OK;
+}
+
 // ---- the merged update: dispatch and body -----------------------------------------
 // The same-list walk over the n rows of list 0 (plan null), or the merge walk
 // over the plan's unique rows.
@@ -1303,6 +1657,7 @@ int psg_table_destroy(psg_table* t) {
   if (t->slots) (void)hipFree(t->slots);
   if (t->mom) (void)hipFree(t->mom);
   if (t->any_buf) (void)hipFree(t->any_buf);
+  if (t->gate) (void)hipFree(t->gate);
   if (t->flags_host) (void)hipHostFree(t->flags_host);
   delete t;
   return PSG_OK;
@@ -1405,6 +1760,14 @@ int psg_table_assign(psg_table* t, const uint64_t* keys, const void* rows, const
 int psg_table_export(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out, void* rows_out,
                      double* m_out, double* v_out, psg_stream stream) {
   return export_rows(t, first, count, keys_out, rows_out, m_out, v_out, stream);
+}
+
+int psg_table_lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* found, uint64_t n, psg_stream stream) {
+  return lookup(t, keys, out, found, n, stream);
+}
+
+int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* erased_host, psg_stream stream) {
+  return erase(t, keys, n, erased_host, stream);
 }
 
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {

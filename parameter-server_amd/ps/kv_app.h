@@ -1475,7 +1475,8 @@ int KVWorker<Value>::SendAny(const SVector<Key>& keys, const SVector<Value>* val
     if (push && pull) return ZPushPull(keys, *vals, outs, nullptr, cmd, cb, priority);
     return push ? ZPush(keys, *vals, {}, cmd, cb, priority) : ZPull(keys, outs, nullptr, cmd, cb, priority);
   }
-  if (push) CHECK(vals->on_device()) << "HBM keys need HBM values";
+  // (a Push without values — the row handles' kRowErase — carries only keys)
+  if (push && vals->size()) CHECK(vals->on_device()) << "HBM keys need HBM values";
   if (pull) CHECK(outs->on_device() && outs->size()) << "HBM keys need a sized HBM output";
   const int dev = keys.device();
   psg_stream st = device::ThreadStream();
@@ -1505,7 +1506,7 @@ int KVWorker<Value>::SendAny(const SVector<Key>& keys, const SVector<Value>* val
   }
   kvs.keys = rkeys;
   SVector<Value> rvals;
-  if (push) {
+  if (push && vals->size()) {  // no values: nothing to gather (psg_rows_gather refuses rows of 0 bytes)
     const size_t row = vals->size() / n * sizeof(Value);
     rvals = SVector<Value>::OnDevice(vals->size(), dev);
     stage::Scope t("worker.route.gather", 2 * vals->size() * sizeof(Value));
@@ -1589,7 +1590,7 @@ int KVWorker<Value>::SendAnyHost(const std::vector<Key>& keys, const std::vector
     for (size_t i = 0; i < n; ++i) (*perm)[at[owner[i]]++] = (uint32_t)i;
     kvs.keys = SVector<Key>::Uninitialized(n);
     for (size_t r = 0; r < n; ++r) kvs.keys[r] = keys[(*perm)[r]];
-    if (push) {
+    if (push && vals->size()) {  // no values: the routed request carries only keys
       const size_t per = vals->size() / n;
       kvs.vals = SVector<Value>::Uninitialized(vals->size());
       for (size_t r = 0; r < n; ++r)

@@ -9,6 +9,8 @@
 //
 //   Push:  row(key_i)[j] += vals[i * width + j]
 //   Pull:  res.vals[i * width + j] = row(key_i)[j]    (post-update)
+//   Pull, cmd kRowLookup:  the same without inserting the keys it has not seen
+//   Push, cmd kRowErase:   keys and no values: the named rows are removed
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first
 // request (or by SaveModel / LoadModel, below); an absent key is inserted with
@@ -28,6 +30,18 @@
 #include "ps/row_checkpoint.h"
 
 namespace ps {
+
+// Request cmds the three row handles share, next to their kAccumulate (2):
+//   kRowLookup, on a Pull:  answered through psg_table_lookup — the rows of the
+//                           keys the table holds, zero rows for the others, in
+//                           any order and with repeats, and NOTHING is inserted
+//                           (a plain Pull inserts every key it has not seen);
+//   kRowErase, on a Push:   keys and no values; the keys the table holds are
+//                           removed at once (psg_table_erase), in any order.
+//                           It never counts towards a round or an iteration.
+// A PushPull with either fails the handle's CHECK.
+constexpr int kRowLookup = 3;
+constexpr int kRowErase = 4;
 
 namespace detail {
 
@@ -86,6 +100,42 @@ void ServeRows(const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<
   server->Response(req_meta, res);
 }
 
+// A request with one of the two cmds above, served; false: it is neither.
+template <typename Value>
+bool ServeRowLifecycle(const char* who, psg_table* table, const KVMeta& req_meta, const KVPairs<Value>& req_data,
+                       KVServer<Value>* server, size_t width) {
+  const int cmd = req_meta.cmd;
+  if (cmd != kRowLookup && cmd != kRowErase) return false;
+  CHECK(!(req_meta.push && req_meta.pull))
+      << who << ": a PushPull cannot carry cmd " << cmd << " (kRowLookup goes with a Pull, kRowErase with a Push)";
+  const size_t n = req_data.keys.size();
+  if (req_meta.pull && cmd == kRowLookup) {
+    ServeRows(req_meta, req_data, server, width, "server.handle.rows.lookup",
+              [&](psg_stream s, const Key* keys, const Value*, Value* out) {
+                device::Check(psg_table_lookup(table, keys, out, nullptr, n, s), "psg_table_lookup");
+              });
+    return true;
+  }
+  if (req_meta.push && cmd == kRowErase) {
+    CHECK(req_data.vals.empty()) << who << ": a Push with kRowErase carries keys and no values, this one "
+                                 << req_data.vals.size();
+    ServeRows(req_meta, req_data, server, width, "server.handle.rows.erase",
+              [&](psg_stream s, const Key* keys, const Value*, Value*) {
+                device::Check(psg_table_erase(table, keys, n, nullptr, s), "psg_table_erase");
+              });
+    return true;
+  }
+  return false;  // a Pull with kRowErase, a Push with kRowLookup: the cmd means nothing there
+}
+
+// The rows a handle's table holds now (0 before its first request).
+inline size_t RowTableSize(psg_table* table) {
+  if (!table) return 0;
+  psg_table_info info;
+  device::Check(psg_table_get_info(table, &info), "psg_table_get_info");
+  return (size_t)info.size;
+}
+
 }  // namespace detail
 
 template <typename Value>
@@ -115,6 +165,7 @@ struct KVServerRowHandle {
     CHECK_GE(dt, 0) << "KVServerRowHandle: value type not supported by the HBM table";
     CHECK(req_data.lens.empty()) << "KVServerRowHandle: rows have one fixed width, lens are not supported";
     detail::EnsureRowTable(&state->table, dt, state->width);
+    if (detail::ServeRowLifecycle("KVServerRowHandle", state->table, req_meta, req_data, server, w)) return;
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     if (req_meta.push) CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
     detail::ServeRows(req_meta, req_data, server, w,
@@ -128,6 +179,9 @@ struct KVServerRowHandle {
                                         "psg_table_handle");
                       });
   }
+
+  // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
+  size_t size() const { return detail::RowTableSize(state->table); }
 
   // The table to a file and back (ps/row_checkpoint.h; the reference's
   // SaveModel / USE_OLD_MODEL, LRServer.h:107-115, 36-63).  Called on the server

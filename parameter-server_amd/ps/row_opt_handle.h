@@ -15,6 +15,11 @@
 //                      (psg_table_handle), how a worker seeds rows; the
 //                      moments are untouched.
 //   Pull:              res.vals[i * width + j] = row(key_i)[j].
+//   Pull, cmd 3:       kRowLookup — the same without inserting: a key the table
+//                      does not hold answers with a zero row (psg_table_lookup).
+//   Push, cmd 4:       kRowErase — keys and no values: the named rows and their
+//                      moments are removed at once (psg_table_erase); the
+//                      iteration is untouched.  (Both: ps/row_handle.h.)
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first request
 // (or by SaveModel / LoadModel, which write and read rows, moments and iteration);
@@ -69,6 +74,8 @@ struct KVServerRowOptHandle {
     CHECK_GE(dev, 0) << "KVServerRowOptHandle: the table lives in HBM and this node has no GPU";
     CHECK(req_data.lens.empty()) << "KVServerRowOptHandle: rows have one fixed width, lens are not supported";
     Table();
+    // kRowLookup / kRowErase (ps/row_handle.h): no gradient, no iteration
+    if (detail::ServeRowLifecycle("KVServerRowOptHandle", st.table, req_meta, req_data, server, w)) return;
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     const bool accumulate = req_meta.push && req_meta.cmd == kAccumulate;
     if (req_meta.push) {
@@ -94,6 +101,8 @@ struct KVServerRowOptHandle {
   }
 
   int iteration() const { return state->iteration; }
+  // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
+  size_t size() const { return detail::RowTableSize(state->table); }
 
   // Rows, moments and the iteration to a file and back (ps/row_checkpoint.h; the
   // reference's SaveModel / USE_OLD_MODEL, LRServer.h:107-115, 36-63).  Called on

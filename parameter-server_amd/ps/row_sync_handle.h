@@ -22,6 +22,12 @@
 //   Push, cmd 2:       kAccumulate — row(key_i)[j] += vals[i * width + j], at
 //                      once (psg_table_handle_any); the moments are untouched.
 //   Pull:              res.vals[i * width + j] = row(key_i)[j], at once.
+//   Pull, cmd 3:       kRowLookup — the same without inserting: a key the table
+//                      does not hold answers with a zero row (psg_table_lookup).
+//   Push, cmd 4:       kRowErase — keys and no values: the named rows and their
+//                      moments are removed at once (psg_table_erase); it is not
+//                      held, does not count towards the round and leaves the
+//                      iteration alone.  (Both: ps/row_handle.h.)
 //
 // The iteration goes up by one after a round is applied, if the round held
 // worker 0's Push with cmd == 1.  The reference counts when that Push arrives
@@ -92,6 +98,8 @@ struct KVServerRowSyncHandle {
     CHECK(nw <= kMaxWorkers) << "KVServerRowSyncHandle: a round merges at most " << kMaxWorkers << " workers, the job has "
                              << nw;
     Table();
+    // kRowLookup / kRowErase (ps/row_handle.h): at once, as cmd 2; neither joins a round
+    if (detail::ServeRowLifecycle("KVServerRowSyncHandle", st.table, req_meta, req_data, server, w)) return;
     if (req_meta.push) {
       CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
       CHECK(req_meta.cmd >= 0 && req_meta.cmd <= kAccumulate) << "KVServerRowSyncHandle: unknown Push cmd " << req_meta.cmd;
@@ -124,6 +132,8 @@ struct KVServerRowSyncHandle {
   }
 
   int iteration() const { return state->iteration; }
+  // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
+  size_t size() const { return detail::RowTableSize(state->table); }
 
   // Rows, moments and the iteration to a file and back, as
   // KVServerRowOptHandle::SaveModel / LoadModel; between rounds only: a round

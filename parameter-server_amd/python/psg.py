@@ -52,6 +52,7 @@ EXPORTS = [
     "psg_table_dump", "psg_table_set_adam", "psg_table_update", "psg_table_dump_moments",
     "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
+    "psg_table_lookup", "psg_table_erase",
     "psg_route", "psg_rows_gather", "psg_rows_scatter",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
@@ -165,6 +166,8 @@ def lib() -> C.CDLL:
             "psg_table_get_adam": ([vp, C.POINTER(i32), C.POINTER(f64)], i32),
             "psg_table_assign": ([vp, vp, vp, vp, vp, u64, vp], i32),
             "psg_table_export": ([vp, u64, u64, vp, vp, vp, vp, vp], i32),
+            "psg_table_lookup": ([vp, vp, vp, vp, u64, vp], i32),
+            "psg_table_erase": ([vp, vp, u64, C.POINTER(u64), vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -609,6 +612,19 @@ class Table:
         (psg_table_export); stream-ordered: synchronise before reading."""
         _call("psg_table_export", self.h, first, count, _ptr(keys_out), _ptr(rows_out), _ptr(m_out), _ptr(v_out),
               _s(stream))
+
+    def lookup(self, keys, out, found, n: int, stream=None) -> None:
+        """Read the rows of n device keys in any order without inserting
+        (psg_table_lookup): out gets each row as bytes, or zeros for an absent
+        key; found (n device bytes) gets 1 / 0.  Either may be None."""
+        _call("psg_table_lookup", self.h, _ptr(keys), _ptr(out), _ptr(found), n, _s(stream))
+
+    def erase(self, keys, n: int, stream=None) -> int:
+        """Remove the keys of the list that are present (psg_table_erase); any
+        order, repeats and absent keys allowed.  Returns the rows removed."""
+        erased = C.c_uint64(0)
+        _call("psg_table_erase", self.h, _ptr(keys), n, C.byref(erased), _s(stream))
+        return erased.value
 
     def close(self) -> None:
         if self.h.value:
