@@ -24,6 +24,10 @@
  *   psg_table_update_merged
  *                    its sync-mode round on rows: k frames merged per key from
  *                    zero, one optimizer step           tests/src/LRServer.h:151-178
+ *   psg_table_lookup_pooled / _update_pooled
+ *                    ids in bags, one row per bag: the bag's rows summed, and
+ *                    that round with the bag's gradient row for each of its ids
+ *                    (no pooling in the reference)
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
  *   psg_slice        KVWorker<V>::DefaultSlicer           src/ps/KVApp.h:515-574
  *   psg_merge        the AddPullCB merge lambda           src/ps/KVApp.h:673-726
@@ -672,6 +676,65 @@ int psg_table_lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* fou
  * state; keys are no longer read. */
 int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* erased_host,
                     psg_stream stream);
+
+/* Pooled lookup: the rows of a BAG of ids summed (EmbeddingBag with sum
+ * pooling), one row per bag across the interface instead of one per id.  The
+ * reference has no pooling: its server answers one value run per key
+ * (KVServerDefaultHandle, src/ps/KVApp.h:446-454) and a model sums them itself.
+ * Built from psg_table_lookup's pieces (the any-order resolve, the flag words on
+ * the device) and never inserts, as psg_table_lookup never does.
+ * keys: n device ids in ANY order and with repeats, inside a bag and across
+ * bags.  offsets: nb + 1 device words; bag b is positions [offsets[b],
+ * offsets[b+1]) of keys: offsets[0] == 0, offsets non-decreasing, offsets[nb]
+ * == n; empty bags are allowed.  out: nb * width elements of the table's dtype
+ * on the device.  For every bag b and column c:
+ *   acc = +0                          -- f32 for F32 / F16 / BF16 tables, f64 for F64
+ *   for p in offsets[b] .. offsets[b+1]-1, in that order:
+ *     if keys[p] is present: acc = acc + (acc_t)row(keys[p])[c]   -- one add each
+ *   out[b*width + c] = (dtype)acc     -- halves: one round-to-nearest-even, at the end
+ * An absent id adds nothing and is NOT inserted; an empty bag, or a bag of
+ * absent ids, gives a row of +0 (and a bag of -0.0 rows too: the sum starts
+ * from +0).  The table is unchanged as psg_table_lookup leaves it: size,
+ * capacity, keys, rows, moments and the device pointers of psg_table_info;
+ * nothing is allocated but request scratch.
+ * Refused with PSG_ERR_INVALID before any device call, in this order: a null
+ * table; null keys with n > 0; null offsets or null out with nb > 0; nb == 0
+ * with n > 0.  Then with PSG_ERR_RANGE: n or nb above 2^32 - 2.  nb == 0 is a
+ * no-op.  Found on the device, and then out is not written: an offsets array
+ * that breaks one of its three rules -> PSG_ERR_INVALID; a key outside
+ * [key_begin, key_end) -> PSG_ERR_RANGE; both -> PSG_ERR_INVALID.  The offsets
+ * are checked by a kernel in front of everything else that reads them, and the
+ * pooling kernel reads both flags on the device and walks nothing it refused:
+ * three kernels and ONE host synchronisation, at the end.  Returns as
+ * psg_table_lookup: keys and offsets are no longer read, out is in memory. */
+int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, void* out,
+                            uint64_t n, uint64_t nb, psg_stream stream);
+/* Pooled update: the backward of the pooled lookup.  grads: nb * width floats
+ * on the device, ONE gradient row per bag, which every id of the bag receives.
+ * keys, offsets, n, nb as psg_table_lookup_pooled.  Rows, Adam moments, keys
+ * and size end, bit for bit, as after
+ *   psg_table_update_merged(t, PSG_PUSH, 1, {keys}, {n}, {E}, NULL, lr, iteration,
+ *                           stream, NULL)
+ * with E[i*width + c] = grads[bag(i)*width + c], bag(i) the bag that holds
+ * position i — the sync-mode round of tests/src/LRServer.h:151-178 on one frame;
+ * E is never built.  For every id named anywhere its bags' gradient rows are
+ * summed from +0.0f in arrival order of its occurrences, one f32 add each, then
+ * the optimizer steps ONCE (SGD, or Adam after psg_table_set_adam; LRServer.h:
+ * 182-189, tests/src/Adam.h:28-34).  An absent id is inserted once with a zero
+ * row and zero moments, then updated.  An empty bag's gradient row is not read.
+ * The reference has no pooling here either.  F32 tables only
+ * (PSG_ERR_UNSUPPORTED).  Refused before any device call as the lookup refuses,
+ * with grads in out's place, and iteration < 0 with PSG_ERR_INVALID.  The
+ * offsets are checked before anything else reads them and every key against
+ * the range before the first write: bad offsets -> PSG_ERR_INVALID, a key out
+ * of range -> PSG_ERR_RANGE (both: PSG_ERR_INVALID), and keys, rows, moments
+ * and size stay bit for bit unchanged.  A strictly ascending list is served
+ * without a sort, as PSG_MERGED_SAME_LIST is for one frame.  Returns as
+ * psg_table_update_merged: keys, offsets and grads are no longer read.
+ * nb == 0 is a no-op. */
+int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets,
+                            const float* grads, uint64_t n, uint64_t nb, float lr, int iteration,
+                            psg_stream stream);
 
 /* ======================================================================== */
 /* Worker side: key-range slicing and pull merge                              */

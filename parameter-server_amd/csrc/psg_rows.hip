@@ -63,6 +63,15 @@
 // device (k_rows_read): two kernels, one synchronisation.  An erase marks the
 // named slots, compacts the survivors in order and gathers keys, rows and
 // moment rows into new arrays (k_rows_take): insert_missing backwards.
+//
+// The pooled calls (psg_table_lookup_pooled / psg_table_update_pooled) serve a
+// sparse feature as its model consumes it: ids in bags (offsets[nb + 1]), one
+// row per BAG across the interface.  The reference has no pooling; the forward
+// is the lookup's two kernels with k_rows_pool in k_rows_read's place (a lane
+// sums its unit of a bag's rows in arrival order and stores once), the backward
+// is the merged round's front half on one list with the bag's gradient row in
+// every occurrence's place (k_bag_of, k_rows_walk_pool).  k_offsets_check runs
+// in front of either, and nothing walks an offsets array it refused.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -105,8 +114,9 @@ constexpr int kRowTile = 1024;  // request keys per block of the resolve (4 per 
 constexpr uint32_t kAbsent = 0xffffffffu;
 constexpr uint64_t kMaxRows = 0xfffffffeull;
 
-// R_DIFFER: raised by k_keys_differ (psg_table_update_merged), after the resolve
-enum { R_MISSING = 0, R_RANGE = 1, R_UNSORTED = 2, R_DIFFER = 3, kNFlags = 4 };
+// R_DIFFER: raised by k_keys_differ (psg_table_update_merged), after the resolve;
+// R_OFFSETS: raised by k_offsets_check (the pooled calls), in front of it
+enum { R_MISSING = 0, R_RANGE = 1, R_UNSORTED = 2, R_DIFFER = 3, R_OFFSETS = 4, kNFlags = 5 };
 
 __device__ __forceinline__ void raise(int* flags, int which, bool cond) {
   if (__ballot(cond) && (threadIdx.x & 63) == 0) flags[which] = 1;
@@ -420,6 +430,46 @@ template <typename UU> struct ReadUnit {
   __device__ __forceinline__ void reply(U* out, uint64_t ro) const { out[ro] = s; }
 };
 
+// Pool (psg_table_lookup_pooled): what a lane keeps of one bag while it sums it.
+// U is the unit as the table stores it (a 16-B vector, or one element), A the
+// running sum: f32 for F32 / F16 / BF16 rows, f64 for F64 rows, one lane of A per
+// element of the unit.  add is ONE add per element, in the accumulator's type;
+// round takes the sum back to the table's type (halves: one round-to-nearest-
+// even, at the end).  The sum starts from A{}: +0 in every lane.
+template <int DT> struct PoolVec;  // the 16-B unit as elements, and its accumulator
+template <> struct PoolVec<PSG_F32> {
+  typedef f32x4 V;
+  typedef f32x4 A;
+};
+template <> struct PoolVec<PSG_F64> {
+  typedef f64x2 V;
+  typedef f64x2 A;
+};
+template <> struct PoolVec<PSG_F16> {
+  typedef Elem<PSG_F16>::h8 V;
+  typedef Elem<PSG_F16>::f8 A;
+};
+template <> struct PoolVec<PSG_BF16> {
+  typedef Elem<PSG_BF16>::b8 V;
+  typedef Elem<PSG_BF16>::f8 A;
+};
+template <int DT, bool VEC> struct PoolAcc;
+template <int DT> struct PoolAcc<DT, true> {
+  typedef u32x4 U;
+  typedef typename PoolVec<DT>::V V;
+  typedef typename PoolVec<DT>::A A;
+  __device__ static __forceinline__ A add(A a, U v) {
+    return a + __builtin_convertvector(__builtin_bit_cast(V, v), A);
+  }
+  __device__ static __forceinline__ U round(A a) { return __builtin_bit_cast(U, __builtin_convertvector(a, V)); }
+};
+template <int DT> struct PoolAcc<DT, false> {
+  typedef typename Elem<DT>::T U;
+  typedef typename std::conditional<DT == PSG_F64, double, float>::type A;
+  __device__ static __forceinline__ A add(A a, U v) { return a + (A)v; }
+  __device__ static __forceinline__ U round(A a) { return (U)a; }
+};
+
 // ---- the optimizer update ----------------------------------------------------
 // Where in its half (m or v) of a moment row the moment of column j lives.
 // width % 4 == 0: the unit of four columns 4u..4u+3 keeps the pair (4u, 4u+1)
@@ -626,6 +676,69 @@ __global__ __launch_bounds__(256) void k_rows_read(const U* __restrict__ R, cons
 #pragma unroll
       for (int k = 0; k < UN; ++k)
         if (ok[k]) u[k].reply(out, ro[k]);
+    }
+  }
+}
+
+// ---- the pooled lookup (psg_table_lookup_pooled) -----------------------------------
+// The three rules of a bag list, over its nb + 1 words: offsets[0] == 0, no
+// offset above its successor, offsets[nb] == n.  Together they put every bag
+// inside [0, n).  8 B read per bag; it runs in front of everything else that
+// reads `offsets`, and a kernel behind it that finds R_OFFSETS raised walks nothing.
+__global__ __launch_bounds__(256) void k_offsets_check(const uint64_t* __restrict__ offsets, uint64_t nb, uint64_t n,
+                                                       int* __restrict__ flags) {
+  int bad = 0;
+  for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b <= nb; b += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t o = offsets[b];
+    if (b == 0 && o != 0) bad = 1;
+    if (b == nb ? o != n : offsets[b + 1] < o) bad = 1;
+  }
+  raise(flags, R_OFFSETS, bad != 0);
+}
+
+// Pass 2 of psg_table_lookup_pooled, launched behind k_offsets_check and
+// k_rows_resolve_any WITHOUT the host in between, as k_rows_read is: `gate` is
+// the device word both raised their flags in, and a launch that finds R_RANGE
+// or R_OFFSETS set returns before it has read one offset — a refused offsets
+// array would send the walk out of `slots`.  Lanes take (bag, unit) pairs as
+// k_rows_walk_seg takes (unique row, unit) pairs.  A lane walks its bag's slots
+// in arrival order, adds its unit of every present row to a sum that starts
+// from +0 (ACC: PoolAcc) and stores once: one writer per unit of the reply, no
+// atomics, no LDS.  The loop is a chain slots -> row unit -> add; the slot two
+// ahead and the row unit one ahead are loaded before the current add.  An
+// absent slot (kAbsent) loads nothing and adds nothing.
+template <typename U, typename ACC>
+__global__ __launch_bounds__(256) void k_rows_pool(const U* __restrict__ R, const uint32_t* __restrict__ slots,
+                                                   const uint64_t* __restrict__ offsets, U* __restrict__ out,
+                                                   uint64_t nb, uint32_t upr, uint32_t rpt,
+                                                   const int* __restrict__ gate) {
+  if (gate[R_RANGE] | gate[R_OFFSETS]) return;
+  const uint64_t ntiles = (nb + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t b0 = t * rpt;
+    const uint32_t nr = (uint32_t)(nb - b0 < rpt ? nb - b0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
+      const uint64_t b = b0 + w.r;
+      const uint32_t c = w.c;
+      uint32_t p = (uint32_t)offsets[b];  // <= n <= 2^32 - 2: checked
+      const uint32_t pe = (uint32_t)offsets[b + 1];
+      typename ACC::A acc = {};  // +0
+      if (p < pe) {
+        uint32_t s0 = slots[p];
+        uint32_t s1 = p + 1 < pe ? slots[p + 1] : kAbsent;
+        U v = {};
+        if (s0 != kAbsent) v = R[(uint64_t)s0 * upr + c];
+        for (; p < pe; ++p) {
+          const uint32_t s2 = p + 2 < pe ? slots[p + 2] : kAbsent;
+          U vn = {};
+          if (s1 != kAbsent) vn = R[(uint64_t)s1 * upr + c];
+          if (s0 != kAbsent) acc = ACC::add(acc, v);
+          s0 = s1, s1 = s2, v = vn;
+        }
+      }
+      out[b * upr + c] = ACC::round(acc);
     }
   }
 }
@@ -932,6 +1045,87 @@ __global__ __launch_bounds__(256) void k_rows_walk_merge(typename UNIT::U* __res
   }
 }
 
+// ---- the pooled update (psg_table_update_pooled) ------------------------------------
+// bag_of[i] for every position i < n of the id list: the bag b with
+// offsets[b] <= i < offsets[b + 1] (offsets checked: k_offsets_check).  A block
+// takes kBlock bags, keeps their kBlock + 1 offsets in LDS and writes the
+// stretch of positions they cover, consecutive lanes consecutive words; a lane
+// finds its position's bag in 8 steps over LDS (the last offset <= i: empty bags
+// share an offset with the bag behind them and own no position).  8 B read per
+// bag, 4 B written per id — and a per-occurrence search of `offsets` in global
+// memory is kept out of the walk's gradient chain.
+__global__ __launch_bounds__(256) void k_bag_of(const uint64_t* __restrict__ offsets, uint64_t nb,
+                                                uint32_t* __restrict__ bag_of) {
+  __shared__ uint32_t off[kBlock + 1];
+  const uint64_t ntiles = (nb + kBlock - 1) / kBlock;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t b0 = t * kBlock;
+    const uint32_t nr = (uint32_t)(nb - b0 < kBlock ? nb - b0 : kBlock);
+    for (uint32_t j = threadIdx.x; j <= nr; j += kBlock) off[j] = (uint32_t)offsets[b0 + j];
+    __syncthreads();
+    const uint32_t p1 = off[nr];
+    for (uint64_t p = (uint64_t)off[0] + threadIdx.x; p < p1; p += kBlock) {  // 64 bits: p1 may be 2^32 - 2
+      uint32_t lo = 0, hi = nr;  // off[lo] <= p < off[hi]
+      while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= p) lo = mid;
+        else hi = mid;
+      }
+      bag_of[p] = (uint32_t)(b0 + lo);
+    }
+    __syncthreads();
+  }
+}
+
+// Pass 2 of psg_table_update_pooled: k_rows_walk_merge's walk on ONE gradient
+// array with a row per bag.  Unique row u (slot slots[u]) for u < m; its
+// occurrences are the sorted positions seg[u] .. seg[u + 1), in arrival order,
+// and bags[p] is the bag of the occurrence at sorted position p — the sort
+// carried bag_of as its payload, so bags IS bag_of[perm[.]] and the chain is
+// bags -> gradient -> add, as the merged walk's is perm -> gradient -> add: the
+// bag two ahead and the gradient unit one ahead are loaded before the current
+// add.  The sum starts from +0.0f, then one step and one store: one writer per
+// row, no atomics.  No Frames, no frame_of, no LDS, no Pull leg.  STRICT: the
+// list ascends strictly, nothing was sorted; row u's one occurrence is position
+// u, bags is bag_of itself and seg is not read.
+template <typename UNIT, bool STRICT>
+__global__ __launch_bounds__(256) void k_rows_walk_pool(typename UNIT::U* __restrict__ R, double* __restrict__ M,
+                                                        const uint32_t* __restrict__ slots,
+                                                        const uint32_t* __restrict__ seg,
+                                                        const uint32_t* __restrict__ bags,
+                                                        const typename UNIT::U* __restrict__ grads, uint64_t m,
+                                                        uint32_t upr, uint32_t rpt, typename UNIT::Params prm) {
+  using U = typename UNIT::U;
+  const uint64_t ntiles = (m + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t u0 = t * rpt;
+    const uint32_t nr = (uint32_t)(m - u0 < rpt ? m - u0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
+      const uint64_t u = u0 + w.r;
+      const uint32_t c = w.c;
+      const uint32_t p0 = STRICT ? (uint32_t)u : seg[u];
+      const uint32_t pe = STRICT ? (uint32_t)u + 1 : seg[u + 1];  // > p0: every unique key has an occurrence
+      UNIT x;
+      x.locate(slots[u], c, upr, prm);
+      x.load_state(R, M, prm);  // issued here, used after the sum
+      uint32_t b1 = p0 + 1 < pe ? bags[p0 + 1] : 0;
+      U v = UNIT::load_grad(grads, (uint64_t)bags[p0] * upr + c);
+      U s = {};  // +0.0f
+      for (uint32_t p = p0; p < pe; ++p) {
+        const uint32_t b2 = p + 2 < pe ? bags[p + 2] : 0;
+        U vn = v;
+        if (p + 1 < pe) vn = UNIT::load_grad(grads, (uint64_t)b1 * upr + c);
+        s = s + v;
+        b1 = b2, v = vn;
+      }
+      x.step(s, prm);
+      x.store_state(R, M, prm);
+    }
+  }
+}
+
 unsigned grid_for(uint64_t blocks) {
   const uint64_t cap = (uint64_t)max_stream_blocks();
   if (blocks > cap) blocks = cap;
@@ -1112,11 +1306,13 @@ struct AnyPlan {  // the request as unique rows: slots in t->slots[m]
 };
 
 // The n keys in a.k0, all in range: sort (key, position) stably, cut the runs
-// of equal keys, resolve the unique list as a strict request.
-int plan_scratch(psg_table* t, const AnyScratch& a, uint64_t n, AnyPlan* plan, hipStream_t st) {
+// of equal keys, resolve the unique list as a strict request.  payload: the
+// sort carries the n words the caller left in a.p0 instead of the positions,
+// and plan->perm holds them in sorted order (the pooled update's bags).
+int plan_scratch(psg_table* t, const AnyScratch& a, uint64_t n, AnyPlan* plan, hipStream_t st, bool payload = false) {
   int res = 0;
   const int bits = std::max(1, bit_width(t->key_end - 1));  // every key is below key_end
-  PSG_TRY(radix_sort_u64(a.k0, a.p0, n, bits, true, a.k1, a.p1, a.counts, st, &res));
+  PSG_TRY(radix_sort_u64(a.k0, a.p0, n, bits, !payload, a.k1, a.p1, a.counts, st, &res));
   const uint64_t* sorted = res ? a.k1 : a.k0;
   uint64_t* U = res ? a.k0 : a.k1;
   compact_count(n, a.counts, RunHead{sorted}, st);
@@ -1606,6 +1802,155 @@ int update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys, c
   return PSG_OK;
 }
 
+// ---- the pooled calls: dispatch and bodies -------------------------------------------
+// What both refuse before any device call, in the header's order; `rows` is the
+// forward's out or the backward's grads.
+int pooled_args(const char* name, const psg_table* t, const uint64_t* keys, const uint64_t* offsets, const void* rows,
+                const char* rows_name, uint64_t n, uint64_t nb) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  PSG_REQUIRE(keys || n == 0, PSG_ERR_INVALID, "%s: null keys", name);
+  PSG_REQUIRE(offsets || nb == 0, PSG_ERR_INVALID, "%s: null offsets", name);
+  PSG_REQUIRE(rows || nb == 0, PSG_ERR_INVALID, "%s: null %s", name, rows_name);
+  PSG_REQUIRE(nb > 0 || n == 0, PSG_ERR_INVALID, "%s: %llu keys and no bag to hold them", name,
+              (unsigned long long)n);
+  return PSG_OK;
+}
+
+int require_offsets(const psg_table* t, const char* name, uint64_t n) {
+  PSG_REQUIRE(!t->flags_host[R_OFFSETS], PSG_ERR_INVALID,
+              "%s: offsets do not start at 0, ascend and end at n = %llu", name, (unsigned long long)n);
+  return PSG_OK;
+}
+
+int launch_offsets_check(const uint64_t* offsets, uint64_t n, uint64_t nb, int* flags, hipStream_t st) {
+  k_offsets_check<<<grid_for((nb + kBlock) / kBlock), kBlock, 0, st>>>(offsets, nb, n, flags);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+template <int DT, bool VEC>
+int launch_pool(psg_table* t, const uint64_t* offsets, void* out, uint64_t nb, uint32_t upr, hipStream_t st) {
+  using ACC = PoolAcc<DT, VEC>;
+  using U = typename ACC::U;
+  const uint32_t rpt = rows_per_tile(upr);
+  k_rows_pool<U, ACC><<<grid_for((nb + rpt - 1) / rpt), kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out,
+                                                                         nb, upr, rpt, t->gate);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+template <int DT>
+int pool_dtype(psg_table* t, const uint64_t* offsets, void* out, uint64_t nb, hipStream_t st) {
+  // 16-B units under accumulate_vec's condition for a Pull
+  if (accumulate_vec(t, PSG_PULL, nullptr, out))
+    return launch_pool<DT, true>(t, offsets, out, nb, t->width / Elem<DT>::kVec, st);
+  return launch_pool<DT, false>(t, offsets, out, nb, t->width, st);
+}
+
+int lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, void* out, uint64_t n, uint64_t nb,
+                  psg_stream stream) {
+  const char* name = "psg_table_lookup_pooled";
+  PSG_TRY(pooled_args(name, t, keys, offsets, out, "out", n, nb));
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
+  PSG_REQUIRE(nb <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 bags in one request", name);
+  if (nb == 0) return PSG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(ensure_slots(t, n));
+  if (!t->gate) PSG_HIP(hipMalloc((void**)&t->gate, kNFlags * sizeof(int)));
+  PSG_HIP(hipMemsetAsync(t->gate, 0, kNFlags * sizeof(int), st));
+  PSG_TRY(launch_offsets_check(offsets, n, nb, t->gate, st));
+  if (n) {
+    k_rows_resolve_any<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(
+        keys, n, t->keys, t->size, t->key_begin, t->key_end, t->slots, t->gate);
+    PSG_HIP(hipGetLastError());
+  }
+  switch (t->dtype) {
+    case PSG_F32: PSG_TRY(pool_dtype<PSG_F32>(t, offsets, out, nb, st)); break;
+    case PSG_F64: PSG_TRY(pool_dtype<PSG_F64>(t, offsets, out, nb, st)); break;
+    case PSG_F16: PSG_TRY(pool_dtype<PSG_F16>(t, offsets, out, nb, st)); break;
+    default: PSG_TRY(pool_dtype<PSG_BF16>(t, offsets, out, nb, st)); break;
+  }
+  // the one synchronisation: keys and offsets no longer read, the reply in memory, the flags on the host
+  PSG_HIP(hipMemcpyAsync(t->flags_host, t->gate, kNFlags * sizeof(int), hipMemcpyDeviceToHost, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  PSG_TRY(require_offsets(t, name, n));
+  return require_in_range(t);
+}
+
+template <typename UNIT>
+int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, const float* grads, uint64_t n,
+                     uint32_t upr, const typename UNIT::Params& prm, hipStream_t st) {
+  using U = typename UNIT::U;
+  const uint32_t rpt = rows_per_tile(upr);
+  const uint64_t rows = p ? p->m : n;
+  const unsigned g = grid_for((rows + rpt - 1) / rpt);
+  if (p)
+    k_rows_walk_pool<UNIT, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, (const U*)grads,
+                                                        rows, upr, rpt, prm);
+  else
+    k_rows_walk_pool<UNIT, true><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, nullptr, bag_of, (const U*)grads,
+                                                       rows, upr, rpt, prm);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+template <bool ADAM>
+int pooled_adam(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, const float* grads, uint64_t n, float lr,
+                int iteration, hipStream_t st) {
+  if (optimize_vec(t, PSG_PUSH, grads, nullptr))
+    return launch_walk_pool<OptUnit<ADAM, true>>(t, p, bag_of, grads, n, t->width / 4,
+                                                 {t->width, lr, adam_args(t, iteration)}, st);
+  return launch_walk_pool<OptUnit<ADAM, false>>(t, p, bag_of, grads, n, t->width,
+                                                {t->width, lr, adam_args(t, iteration)}, st);
+}
+
+int update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads, uint64_t n,
+                  uint64_t nb, float lr, int iteration, psg_stream stream) {
+  const char* name = "psg_table_update_pooled";
+  PSG_TRY(pooled_args(name, t, keys, offsets, grads, "grads", n, nb));
+  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
+  PSG_REQUIRE(nb <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 bags in one request", name);
+  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
+  if (nb == 0) return PSG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // resolve_first with the offsets check in front of it: both raise their flags
+  // in t->flags_host, read after one synchronisation; nothing is written yet
+  PSG_TRY(ensure_slots(t, n));
+  memset(t->flags_host, 0, kNFlags * sizeof(int));
+  PSG_TRY(launch_offsets_check(offsets, n, nb, t->flags, st));
+  if (n) {
+    k_rows_resolve<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(keys, n, t->keys, t->size, t->key_begin,
+                                                                              t->key_end, t->slots, t->flags);
+    PSG_HIP(hipGetLastError());
+  }
+  PSG_HIP(hipStreamSynchronize(st));
+  PSG_TRY(require_offsets(t, name, n));
+  PSG_TRY(require_in_range(t));
+  if (n == 0) return PSG_OK;  // every bag is empty: no gradient row is read
+  // bag_of goes where the sort keeps its positions (a.p0): the sorted path sorts
+  // (key, bag) pairs, the strict one reads it as it is
+  const bool strict = !t->flags_host[R_UNSORTED];  // as PSG_MERGED_SAME_LIST is decided for k = 1
+  AnyScratch a;
+  PSG_TRY(any_scratch(t, n, &a));
+  k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, a.p0);
+  PSG_HIP(hipGetLastError());
+  AnyPlan plan;
+  const AnyPlan* p = nullptr;
+  if (strict) {
+    PSG_TRY(resolve_finish(t, keys, n, st));
+  } else {
+    PSG_HIP(hipMemcpyAsync(a.k0, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    PSG_TRY(plan_scratch(t, a, n, &plan, st, true));
+    p = &plan;
+  }
+  PSG_TRY(t->adam ? pooled_adam<true>(t, p, a.p0, grads, n, lr, iteration, st)
+                  : pooled_adam<false>(t, p, a.p0, grads, n, lr, iteration, st));
+  // complete on return: keys, offsets and grads no longer read
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
 }  // namespace
 }  // namespace psg
 
@@ -1768,6 +2113,16 @@ int psg_table_lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* fou
 
 int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* erased_host, psg_stream stream) {
   return erase(t, keys, n, erased_host, stream);
+}
+
+int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, void* out, uint64_t n,
+                            uint64_t nb, psg_stream stream) {
+  return lookup_pooled(t, keys, offsets, out, n, nb, stream);
+}
+
+int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads,
+                            uint64_t n, uint64_t nb, float lr, int iteration, psg_stream stream) {
+  return update_pooled(t, keys, offsets, grads, n, nb, lr, iteration, stream);
 }
 
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {

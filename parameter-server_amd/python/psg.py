@@ -52,7 +52,7 @@ EXPORTS = [
     "psg_table_dump", "psg_table_set_adam", "psg_table_update", "psg_table_dump_moments",
     "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
-    "psg_table_lookup", "psg_table_erase",
+    "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
     "psg_route", "psg_rows_gather", "psg_rows_scatter",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
@@ -168,6 +168,8 @@ def lib() -> C.CDLL:
             "psg_table_export": ([vp, u64, u64, vp, vp, vp, vp, vp], i32),
             "psg_table_lookup": ([vp, vp, vp, vp, u64, vp], i32),
             "psg_table_erase": ([vp, vp, u64, C.POINTER(u64), vp], i32),
+            "psg_table_lookup_pooled": ([vp, vp, vp, vp, u64, u64, vp], i32),
+            "psg_table_update_pooled": ([vp, vp, vp, vp, u64, u64, f32, i32, vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -625,6 +627,19 @@ class Table:
         erased = C.c_uint64(0)
         _call("psg_table_erase", self.h, _ptr(keys), n, C.byref(erased), _s(stream))
         return erased.value
+
+    def lookup_pooled(self, keys, offsets, out, n: int, nb: int, stream=None) -> None:
+        """Sum the rows of each bag of ids without inserting (psg_table_lookup_pooled):
+        bag b is keys[offsets[b] : offsets[b + 1]] (nb + 1 device uint64 offsets),
+        out gets nb rows; an absent id adds nothing."""
+        _call("psg_table_lookup_pooled", self.h, _ptr(keys), _ptr(offsets), _ptr(out), n, nb, _s(stream))
+
+    def update_pooled(self, keys, offsets, grads, n: int, nb: int, lr: float, iteration: int, stream=None) -> None:
+        """The pooled lookup's backward (psg_table_update_pooled): grads holds one
+        gradient row per BAG; every id sums the rows of the bags it occurs in, in
+        arrival order, and takes one optimizer step."""
+        _call("psg_table_update_pooled", self.h, _ptr(keys), _ptr(offsets), _ptr(grads), n, nb, lr, iteration,
+              _s(stream))
 
     def close(self) -> None:
         if self.h.value:
