@@ -34,6 +34,10 @@
  *   psg_route / psg_rows_gather / psg_rows_scatter
  *                    DefaultSlicer for a list in any order and with repeats
  *                                                        src/ps/KVApp.h:515-574
+ *   psg_route_bags / psg_pool_reduce
+ *                    the bags of a routed list cut into the servers' shares, and
+ *                    the servers' pooled rows added in rank order (no pooling in
+ *                    the reference)
  *   psg_comm_*       the ZMQ data path of Van::Send / ZMQVan::SendMsg / ReceiveMsg
  *                    (src/internal/Van.cpp:170-179, src/internal/ZMQVan.cpp:147-248)
  *                    for the BSP case: Push = reduce-scatter + accumulate,
@@ -818,6 +822,66 @@ int psg_rows_gather(void* dst, const void* src, const uint32_t* perm, uint64_t n
                     uint64_t row_bytes, psg_stream stream);
 int psg_rows_scatter(void* dst, const void* src, const uint32_t* perm, uint64_t n,
                      uint64_t row_bytes, psg_stream stream);
+
+/* Bags across servers: psg_table_lookup_pooled / _update_pooled on a table that
+ * is sharded over ns servers by key range.  The reference has no pooling.
+ * keys[n] (any order, repeats) and offsets[nb + 1] as psg_table_lookup_pooled;
+ * psg_route gives the list's stable partition by owner, perm and key_pos[ns+1].
+ * Server s's share of bag b is the ids of bag b that s owns, in arrival order.
+ * Bags are contiguous and the partition is stable, so that share is the
+ * stretch [so[s][b], so[s][b+1]) of s's routed stretch, with
+ *   so[s][b] = #{ r in [key_pos[s], key_pos[s+1]) : perm[r] < offsets[b] }
+ * (identity route: clamp(offsets[b], key_pos[s], key_pos[s+1]) - key_pos[s]).
+ * FORWARD.  P_s = psg_table_lookup_pooled on server s of its stretch with the
+ * offsets so[s]: nb * width elements, a bag with no id on s a row of +0.  The
+ * result, per element i:
+ *   acc = (acc_t)+0
+ *   for s = 0 .. ns-1, in rank order:  acc = acc + (acc_t)P_s[i]   -- one add each
+ *   out[i] = (dtype)acc        -- halves: one round-to-nearest-even, at the end
+ * acc_t: f32 for F32 / F16 / BF16, f64 for F64.  A server that owns none of the
+ * list's ids may be skipped: its partial is all +0, and acc + (+0) == acc for
+ * every value acc takes here (acc starts at +0 and is never -0; a pooled partial
+ * is never -0 either).  So at ns == 1 the result is psg_table_lookup_pooled's on
+ * one table, bit for bit.  At ns > 1 a bag that spans servers is NOT summed in
+ * the single table's arrival order: ids are added per server first, then the
+ * servers in rank order.  That is the one deviation, and it is this definition.
+ * BACKWARD.  Server s runs psg_table_update_pooled(keys_s, so[s], grads, n_s,
+ * nb, lr, iteration) on its stretch with the WHOLE gradient array grads[nb *
+ * width].  Every occurrence of an id goes to one server, in arrival order, so
+ * keys, rows, Adam moments and sizes over all servers end, bit for bit, as one
+ * table over the whole range after psg_table_update_pooled on the whole list.
+ *
+ * psg_route_bags writes so: server_offsets (device) holds ns * (nb + 1) words,
+ * server s's offsets at [s * (nb + 1), (s + 1) * (nb + 1)).  offsets: device,
+ * nb + 1 words; perm: psg_route's (device, n words), or NULL for a list it left
+ * in place (*identity_host == 1), when so is the clamp and nothing is searched;
+ * key_pos_host: psg_route's ns + 1 bounds.  A checking kernel runs first and
+ * applies the three offsets rules (offsets[0] == 0, non-decreasing, offsets[nb]
+ * == n); the kernel behind it writes nothing when one is broken, and the call
+ * fails with PSG_ERR_INVALID after its ONE synchronisation, at the end:
+ * server_offsets is then untouched and the caller must send nothing.  Refused
+ * before any device call, in this order, with PSG_ERR_INVALID: null offsets or
+ * null server_offsets with nb > 0; null key_pos_host; num_servers outside [1,
+ * PSG_ROUTE_MAX_SERVERS]; key_pos_host not non-decreasing from 0 to n; then
+ * with PSG_ERR_RANGE: n or nb above 2^32 - 2.  nb == 0 is a no-op.  Returns
+ * once server_offsets is in memory.  8 B read and ns * 8 B written per bag,
+ * plus at most 32 probes of perm per word written. */
+int psg_route_bags(const uint64_t* offsets, uint64_t nb, const uint32_t* perm, uint64_t n,
+                   int num_servers, const uint64_t* key_pos_host, uint64_t* server_offsets,
+                   psg_stream stream);
+/* The forward fold above: out[i] from the k partials, partials_host[0] first,
+ * for i < count elements of `dtype` (PSG_F32 / F64 / F16 / BF16).
+ * partials_host: k device pointers in host memory, read before the call
+ * returns (they ride in the kernel's arguments); 1 <= k <=
+ * PSG_ROUTE_MAX_SERVERS.  16-B vectors when out, every partial and count *
+ * sizeof(T) allow, else elements.  One writer per element, no atomics; (k + 1)
+ * * sizeof(T) bytes of traffic an element.  Stream-ordered.  out may not
+ * overlap a partial.  Refused with PSG_ERR_INVALID before any device call: k
+ * out of range, an unknown dtype, null out / partials_host / partial with count
+ * > 0, a pointer not aligned to its element, out overlapping a partial.
+ * count == 0 is a no-op. */
+int psg_pool_reduce(void* out, const void* const* partials_host, int k, uint64_t count, int dtype,
+                    psg_stream stream);
 
 /* One pull reply (KVPairs from one server, KVApp.h:631-637). */
 typedef struct psg_segment {

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <deque>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/psg.h"
@@ -115,6 +116,48 @@ template <> struct Elem<PSG_BF16> {
   }
   __device__ static inline T add1(T a, T b) { return (T)((float)a + (float)b); }
 };
+
+#ifdef __HIPCC__
+// A pooled sum (psg_table_lookup_pooled's bags, psg_pool_reduce's partials):
+// U is the unit as memory holds it (a 16-B vector, or one element), A the
+// running sum: f32 for F32 / F16 / BF16, f64 for F64, one lane of A per element
+// of the unit.  add is ONE add per element, in the accumulator's type; round
+// takes the sum back to the stored type (halves: one round-to-nearest-even, at
+// the end).  The sum starts from A{}: +0 in every lane.
+template <int DT> struct PoolVec;  // the 16-B unit as elements, and its accumulator
+template <> struct PoolVec<PSG_F32> {
+  typedef f32x4 V;
+  typedef f32x4 A;
+};
+template <> struct PoolVec<PSG_F64> {
+  typedef f64x2 V;
+  typedef f64x2 A;
+};
+template <> struct PoolVec<PSG_F16> {
+  typedef Elem<PSG_F16>::h8 V;
+  typedef Elem<PSG_F16>::f8 A;
+};
+template <> struct PoolVec<PSG_BF16> {
+  typedef Elem<PSG_BF16>::b8 V;
+  typedef Elem<PSG_BF16>::f8 A;
+};
+template <int DT, bool VEC> struct PoolAcc;
+template <int DT> struct PoolAcc<DT, true> {
+  typedef u32x4 U;
+  typedef typename PoolVec<DT>::V V;
+  typedef typename PoolVec<DT>::A A;
+  __device__ static __forceinline__ A add(A a, U v) {
+    return a + __builtin_convertvector(__builtin_bit_cast(V, v), A);
+  }
+  __device__ static __forceinline__ U round(A a) { return __builtin_bit_cast(U, __builtin_convertvector(a, V)); }
+};
+template <int DT> struct PoolAcc<DT, false> {
+  typedef typename Elem<DT>::T U;
+  typedef typename std::conditional<DT == PSG_F64, double, float>::type A;
+  __device__ static __forceinline__ A add(A a, U v) { return a + (A)v; }
+  __device__ static __forceinline__ U round(A a) { return (U)a; }
+};
+#endif
 
 // ---- launch geometry --------------------------------------------------------
 // Streaming kernels: 256-thread blocks, grid capped at 256 CUs x 8 blocks and

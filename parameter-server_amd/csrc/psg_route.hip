@@ -25,6 +25,18 @@
 // The two row copies walk the rows as one flat stream of units, as k_rows_walk
 // (psg_rows.hip) does, kUnroll loads a lane in flight.  perm is a permutation:
 // every row has one writer, no atomics.  Traffic: perm 4 B + 2 * row_bytes a row.
+//
+// Bags across servers (the pooled lookup and update of psg_rows.hip, sharded):
+//   psg_route_bags    every server's share of every bag of a routed list, as
+//                     the nb + 1 offsets of that server's stretch
+//   psg_pool_reduce   the servers' pooled partial rows added in rank order
+//   k_bags_check      the three rules of an offsets array (k_offsets_check's,
+//                     psg_rows.hip), in front of everything else that reads it
+//   k_bags_split      one lane per (server, offset): a lower bound over the
+//                     server's ascending stretch of perm, or a clamp when the
+//                     list was left in place; writes nothing it was refused
+//   k_pool_reduce     one lane per 16-B vector (or element): k loads, k adds
+//                     from +0 in the accumulator's type, one store; no atomics
 #include <algorithm>
 #include <map>
 
@@ -210,6 +222,127 @@ int get_route_scratch(uint64_t words, RouteScratch** out) {
   return PSG_OK;
 }
 
+// ---- bags across servers ------------------------------------------------------
+// The three rules of a bag list (k_offsets_check, psg_rows.hip): offsets[0] == 0,
+// no offset above its successor, offsets[nb] == n.  8 B read per bag.  A broken
+// rule raises *gate (a device word k_bags_split reads) and *flag_host (pinned
+// host memory, read by the host after the one synchronisation).
+__global__ __launch_bounds__(256) void k_bags_check(const uint64_t* __restrict__ offsets, uint64_t nb, uint64_t n,
+                                                    int* __restrict__ gate, int* __restrict__ flag_host) {
+  bool bad = false;
+  for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b <= nb; b += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t o = offsets[b];
+    if (b == 0 && o != 0) bad = true;
+    if (b == nb ? o != n : offsets[b + 1] < o) bad = true;
+  }
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) {
+    *gate = 1;
+    *flag_host = 1;
+  }
+}
+
+struct KeyPos {
+  uint64_t v[kMaxServers + 1];  // key_pos[0 .. ns]
+};
+
+// so[s][b] = #{ r in [key_pos[s], key_pos[s+1]) : perm[r] < offsets[b] }, one lane
+// per (s, b), b in [0, nb].  Server s's stretch of perm ascends (the partition is
+// stable), so the count is a lower bound: at most 32 dependent 4-B probes, over
+// lines the lanes of neighbouring bags share.  IDENT: the list was left in
+// place, perm[r] == r, and the count is a clamp.  Launched behind k_bags_check
+// without the host in between: a launch that finds *gate raised writes nothing.
+// Every read of perm lies inside [0, key_pos[ns]) whatever the offsets hold.
+template <bool IDENT>
+__global__ __launch_bounds__(256) void k_bags_split(const uint64_t* __restrict__ offsets, uint64_t nb,
+                                                    const uint32_t* __restrict__ perm, KeyPos kp, uint32_t ns,
+                                                    uint64_t* __restrict__ so, const int* __restrict__ gate) {
+  __shared__ uint64_t s_kp[kMaxServers + 1];
+  if (threadIdx.x <= (unsigned)kMaxServers) s_kp[threadIdx.x] = kp.v[threadIdx.x];
+  __syncthreads();
+  if (*gate) return;
+  const uint64_t per = nb + 1, total = (uint64_t)ns * per;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t s = i / per;
+    const uint64_t o = offsets[i - s * per];
+    const uint64_t lo = s_kp[s], hi = s_kp[s + 1];
+    uint64_t a = lo, b = hi;
+    if (IDENT) {
+      a = o < lo ? lo : o > hi ? hi : o;
+    } else {
+      while (a < b) {
+        const uint64_t mid = a + ((b - a) >> 1);
+        if (perm[mid] < o) a = mid + 1;
+        else b = mid;
+      }
+    }
+    so[i] = a - lo;
+  }
+}
+
+// Scratch of psg_route_bags, per thread and GPU as the route's: the gate word in
+// HBM and the pinned flag word.
+struct BagScratch {
+  int* gate = nullptr;
+  int* flag_host = nullptr;
+  int* flag_dev = nullptr;  // device view of flag_host
+};
+thread_local std::map<int, BagScratch> t_bag_scratch;
+
+int get_bag_scratch(BagScratch** out) {
+  int dev = 0;
+  PSG_HIP(hipGetDevice(&dev));
+  BagScratch& s = t_bag_scratch[dev];
+  if (!s.flag_host) {
+    PSG_HIP(hipHostMalloc((void**)&s.flag_host, sizeof(int), hipHostMallocMapped));
+    PSG_HIP(hipHostGetDevicePointer((void**)&s.flag_dev, s.flag_host, 0));
+  }
+  if (!s.gate) PSG_HIP(hipMalloc((void**)&s.gate, sizeof(int)));
+  *out = &s;
+  return PSG_OK;
+}
+
+// out unit i = round(((+0 + p[0][i]) + p[1][i]) + ... + p[k-1][i]), the adds in
+// the accumulator's type (PoolAcc): the fold of the servers' pooled partials in
+// rank order.  One lane per unit, grid-strided; four loads of a unit in flight,
+// then their four adds in order.  The pointers ride in the kernel's arguments
+// and are indexed by a wave-uniform s.  (k + 1) * sizeof(U) bytes a unit.
+struct Partials {
+  const void* p[kMaxServers];
+};
+
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void k_pool_reduce(typename PoolAcc<DT, VEC>::U* __restrict__ out, Partials ps, int k,
+                                                     uint64_t units) {
+  typedef PoolAcc<DT, VEC> P;
+  typedef typename P::U U;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < units; i += (uint64_t)gridDim.x * kBlock) {
+    typename P::A acc{};
+    int s = 0;
+    for (; s + 4 <= k; s += 4) {
+      const U v0 = ((const U*)ps.p[s])[i], v1 = ((const U*)ps.p[s + 1])[i];
+      const U v2 = ((const U*)ps.p[s + 2])[i], v3 = ((const U*)ps.p[s + 3])[i];
+      acc = P::add(acc, v0);
+      acc = P::add(acc, v1);
+      acc = P::add(acc, v2);
+      acc = P::add(acc, v3);
+    }
+    for (; s < k; ++s) acc = P::add(acc, ((const U*)ps.p[s])[i]);
+    out[i] = P::round(acc);
+  }
+}
+
+template <int DT>
+int launch_pool_reduce(void* out, const Partials& ps, int k, uint64_t count, bool vec, hipStream_t st) {
+  const uint64_t units = vec ? count / Elem<DT>::kVec : count;
+  const uint64_t blocks = std::min<uint64_t>((units + kBlock - 1) / kBlock, (uint64_t)max_stream_blocks());
+  if (vec)
+    k_pool_reduce<DT, true><<<(unsigned)blocks, kBlock, 0, st>>>((typename PoolAcc<DT, true>::U*)out, ps, k, units);
+  else
+    k_pool_reduce<DT, false><<<(unsigned)blocks, kBlock, 0, st>>>((typename PoolAcc<DT, false>::U*)out, ps, k, units);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
 }  // namespace
 
 }  // namespace psg
@@ -279,6 +412,77 @@ int psg_rows_gather(void* dst, const void* src, const uint32_t* perm, uint64_t n
 int psg_rows_scatter(void* dst, const void* src, const uint32_t* perm, uint64_t n, uint64_t row_bytes,
                      psg_stream stream) {
   return permute_rows<false>("psg_rows_scatter", dst, src, perm, n, row_bytes, (hipStream_t)stream);
+}
+
+int psg_route_bags(const uint64_t* offsets, uint64_t nb, const uint32_t* perm, uint64_t n, int num_servers,
+                   const uint64_t* key_pos_host, uint64_t* server_offsets, psg_stream stream) {
+  PSG_REQUIRE(offsets || nb == 0, PSG_ERR_INVALID, "psg_route_bags: null offsets");
+  PSG_REQUIRE(server_offsets || nb == 0, PSG_ERR_INVALID, "psg_route_bags: null server_offsets");
+  PSG_REQUIRE(key_pos_host, PSG_ERR_INVALID, "psg_route_bags: null key_pos");
+  PSG_REQUIRE(num_servers > 0 && num_servers <= kMaxServers, PSG_ERR_INVALID,
+              "psg_route_bags: %d servers outside [1, %d]", num_servers, kMaxServers);
+  PSG_REQUIRE(key_pos_host[0] == 0 && key_pos_host[num_servers] == n, PSG_ERR_INVALID,
+              "psg_route_bags: key_pos does not run from 0 to n = %llu", (unsigned long long)n);
+  for (int s = 0; s < num_servers; ++s)
+    PSG_REQUIRE(key_pos_host[s] <= key_pos_host[s + 1], PSG_ERR_INVALID, "psg_route_bags: key_pos decreases at server %d",
+                s);
+  PSG_REQUIRE(n <= kMaxRouted && nb <= kMaxRouted, PSG_ERR_RANGE, "psg_route_bags: %llu keys in %llu bags, more than 2^32-2",
+              (unsigned long long)n, (unsigned long long)nb);
+  if (nb == 0) return PSG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  BagScratch* sc = nullptr;
+  PSG_TRY(get_bag_scratch(&sc));
+  KeyPos kp;
+  for (int s = 0; s <= kMaxServers; ++s) kp.v[s] = key_pos_host[s <= num_servers ? s : num_servers];
+  *sc->flag_host = 0;
+  PSG_HIP(hipMemsetAsync(sc->gate, 0, sizeof(int), st));
+  const uint64_t cap = (uint64_t)max_stream_blocks();
+  k_bags_check<<<(unsigned)std::min<uint64_t>((nb + kBlock) / kBlock, cap), kBlock, 0, st>>>(offsets, nb, n, sc->gate,
+                                                                                            sc->flag_dev);
+  const uint64_t total = (uint64_t)num_servers * (nb + 1);
+  const unsigned blocks = (unsigned)std::min<uint64_t>((total + kBlock - 1) / kBlock, cap);
+  if (perm)
+    k_bags_split<false><<<blocks, kBlock, 0, st>>>(offsets, nb, perm, kp, (uint32_t)num_servers, server_offsets, sc->gate);
+  else
+    k_bags_split<true><<<blocks, kBlock, 0, st>>>(offsets, nb, nullptr, kp, (uint32_t)num_servers, server_offsets,
+                                                  sc->gate);
+  PSG_HIP(hipGetLastError());
+  PSG_HIP(hipStreamSynchronize(st));
+  PSG_REQUIRE(!*sc->flag_host, PSG_ERR_INVALID,
+              "psg_route_bags: offsets must start at 0, never decrease and end at n = %llu", (unsigned long long)n);
+  return PSG_OK;
+}
+
+int psg_pool_reduce(void* out, const void* const* partials_host, int k, uint64_t count, int dtype, psg_stream stream) {
+  PSG_REQUIRE(k > 0 && k <= kMaxServers, PSG_ERR_INVALID, "psg_pool_reduce: %d partials outside [1, %d]", k, kMaxServers);
+  const uint64_t es = (uint64_t)dtype_size(dtype);
+  PSG_REQUIRE(es, PSG_ERR_INVALID, "psg_pool_reduce: unknown dtype %d", dtype);
+  PSG_REQUIRE(count <= UINT64_MAX / es, PSG_ERR_RANGE, "psg_pool_reduce: %llu elements overflow a byte count",
+              (unsigned long long)count);
+  if (count == 0) return PSG_OK;
+  PSG_REQUIRE(out && partials_host, PSG_ERR_INVALID, "psg_pool_reduce: null out or partials");
+  const uint64_t bytes = count * es;
+  const uintptr_t o = reinterpret_cast<uintptr_t>(out);
+  uintptr_t a = o | (uintptr_t)bytes;
+  Partials ps;
+  for (int s = 0; s < kMaxServers; ++s) {
+    ps.p[s] = s < k ? partials_host[s] : nullptr;
+    if (s >= k) continue;
+    const uintptr_t p = reinterpret_cast<uintptr_t>(ps.p[s]);
+    PSG_REQUIRE(p, PSG_ERR_INVALID, "psg_pool_reduce: partial %d is null", s);
+    PSG_REQUIRE(p >= o ? p - o >= bytes : o - p >= bytes, PSG_ERR_INVALID, "psg_pool_reduce: out overlaps partial %d", s);
+    a |= p;
+  }
+  PSG_REQUIRE(a % es == 0, PSG_ERR_INVALID, "psg_pool_reduce: a pointer is not aligned to its %llu-byte elements",
+              (unsigned long long)es);
+  const bool vec = a % 16 == 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (dtype) {
+    case PSG_F32: return launch_pool_reduce<PSG_F32>(out, ps, k, count, vec, st);
+    case PSG_F64: return launch_pool_reduce<PSG_F64>(out, ps, k, count, vec, st);
+    case PSG_F16: return launch_pool_reduce<PSG_F16>(out, ps, k, count, vec, st);
+    default: return launch_pool_reduce<PSG_BF16>(out, ps, k, count, vec, st);
+  }
 }
 
 }  // extern "C"

@@ -433,42 +433,7 @@ template <typename UU> struct ReadUnit {
 // Pool (psg_table_lookup_pooled): what a lane keeps of one bag while it sums it.
 // U is the unit as the table stores it (a 16-B vector, or one element), A the
 // running sum: f32 for F32 / F16 / BF16 rows, f64 for F64 rows, one lane of A per
-// element of the unit.  add is ONE add per element, in the accumulator's type;
-// round takes the sum back to the table's type (halves: one round-to-nearest-
-// even, at the end).  The sum starts from A{}: +0 in every lane.
-template <int DT> struct PoolVec;  // the 16-B unit as elements, and its accumulator
-template <> struct PoolVec<PSG_F32> {
-  typedef f32x4 V;
-  typedef f32x4 A;
-};
-template <> struct PoolVec<PSG_F64> {
-  typedef f64x2 V;
-  typedef f64x2 A;
-};
-template <> struct PoolVec<PSG_F16> {
-  typedef Elem<PSG_F16>::h8 V;
-  typedef Elem<PSG_F16>::f8 A;
-};
-template <> struct PoolVec<PSG_BF16> {
-  typedef Elem<PSG_BF16>::b8 V;
-  typedef Elem<PSG_BF16>::f8 A;
-};
-template <int DT, bool VEC> struct PoolAcc;
-template <int DT> struct PoolAcc<DT, true> {
-  typedef u32x4 U;
-  typedef typename PoolVec<DT>::V V;
-  typedef typename PoolVec<DT>::A A;
-  __device__ static __forceinline__ A add(A a, U v) {
-    return a + __builtin_convertvector(__builtin_bit_cast(V, v), A);
-  }
-  __device__ static __forceinline__ U round(A a) { return __builtin_bit_cast(U, __builtin_convertvector(a, V)); }
-};
-template <int DT> struct PoolAcc<DT, false> {
-  typedef typename Elem<DT>::T U;
-  typedef typename std::conditional<DT == PSG_F64, double, float>::type A;
-  __device__ static __forceinline__ A add(A a, U v) { return a + (A)v; }
-  __device__ static __forceinline__ U round(A a) { return (U)a; }
-};
+// element of the unit (PoolAcc, psg_internal.h, which psg_pool_reduce shares).
 
 // ---- the optimizer update ----------------------------------------------------
 // Where in its half (m or v) of a moment row the moment of column j lives.

@@ -84,6 +84,9 @@ struct Meta {
   // reply: a speculative slice this server refused (a key outside its range;
   // nothing applied) — the worker re-sends its keys sliced for real
   bool refused = false;
+  // request: its LAST data frame holds the bag offsets of a pooled request
+  // (KVPairs::offsets, uint64), behind the frames every other request carries
+  bool bags = false;
   std::string body;
   std::vector<DataType> data_type;
   Control control;

@@ -52,6 +52,9 @@ struct KVPairs {
   SVector<Value> vals;
   SVector<int> lens;
   int priority = 0;
+  // a pooled request (ZPullPooled / ZPushPooled): nb + 1 bag offsets into keys,
+  // as psg_table_lookup_pooled takes them; empty on every other request
+  SVector<uint64_t> offsets;
 };
 
 /* meta of one request (KVApp.h:42-57) */
@@ -63,6 +66,12 @@ struct KVMeta {
   int timestamp;
   int customer_id;
 };
+
+// The cmds of KVWorker's pooled calls, which the row handles serve
+// (ps/row_handle.h, next to its kRowLookup = 3 and kRowErase = 4).
+constexpr int kRowLookupPooled = 5;      // ZPullPooled
+constexpr int kRowUpdatePooled = 6;      // ZPushPooled
+constexpr int kRowUpdatePooledStep = 7;  // ZPushPooled(step): also ends worker 0's iteration
 
 namespace detail {
 template <typename T>
@@ -421,6 +430,36 @@ class KVWorker : public SimpleApp {
     CHECK_EQ(vals.size(), outs->size()) << "ZPushPullAny: the output mirrors vals";
     return SendAny(keys, &vals, outs, cmd, cb, priority);
   }
+  /* ---- bags of ids on a table sharded over the servers ---------------------------
+   * keys: n ids in any order and with repeats; offsets: nb + 1 words, bag b is
+   * keys[offsets[b] .. offsets[b+1]) (the rules of psg_table_lookup_pooled); all
+   * in HBM.  The list is routed as the Any calls route it (a list already
+   * partitioned by owner is sent from the caller's own keys), psg_route_bags
+   * cuts every bag into the servers' shares, and every server that owns ids is
+   * sent its stretch of keys and its nb + 1 offsets, for the row handles' cmds
+   * kRowLookupPooled / kRowUpdatePooled / kRowUpdatePooledStep (ps/row_handle.h).
+   * The definition is include/psg.h's ("Bags across servers").
+   * ZPullPooled: out holds nb * k values.  Each server is offered its own
+   *   nb * k frame from the HBM pool; when the last reply is in, psg_pool_reduce
+   *   adds the frames in rank order into out, the frames go back to the pool,
+   *   and then the callback runs; Wait(ts) returns after that.  One server: out
+   *   itself is offered and nothing is reduced.  nb * k values per server come
+   *   back instead of ZPullAny's n * k in all: fewer bytes when bags hold more
+   *   ids than there are servers.
+   * ZPushPooled: grads holds nb * k values, one gradient row per bag; every
+   *   server gets the whole frame.  step: the update also ends worker 0's
+   *   iteration on the servers it reaches, as a Push with cmd 1 does.
+   * CHECKs: no custom slicer; out / grads hold a multiple of nb values;
+   * psg_route_bags did not refuse the offsets (nothing is sent then). */
+  int ZPullPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, SVector<Value>* out,
+                  const Callback& cb = nullptr, int priority = 0) {
+    CHECK_NOTNULL(out);
+    return SendPooled(keys, offsets, nullptr, out, false, cb, priority);
+  }
+  int ZPushPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>& grads,
+                  bool step = false, const Callback& cb = nullptr, int priority = 0) {
+    return SendPooled(keys, offsets, &grads, nullptr, step, cb, priority);
+  }
   /* Host-vector forms: the same routing done on the host (a stable counting
    * pass over the owners), the routed copies sent as host frames on its bounds,
    * the replies un-permuted on the host in the callback.  A correctness path,
@@ -526,6 +565,9 @@ class KVWorker : public SimpleApp {
               int priority);
   int SendAnyHost(const std::vector<Key>& keys, const std::vector<Value>* vals, std::vector<Value>* outs, int cmd,
                   const Callback& cb, int priority);
+  /* ZPullPooled (grads == nullptr) and ZPushPooled (out == nullptr) */
+  int SendPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>* grads,
+                 SVector<Value>* out, bool step, const Callback& cb, int priority);
   void OnReceive(const Message& msg) override;
   void DefaultSlicer(Data& send, const std::vector<Range>& ranges, SlicedKVs* sliced);
   /* routed: the request went out on SendBounds — its keys are partitioned by
@@ -628,7 +670,7 @@ class KVServer : public SimpleApp {
    * for such a PushPull) */
   static bool PlainRequest(const Message& m) {
     if (!m.meta.request || m.meta.simple_app || m.meta.control.cmd != Control::EMPTY) return false;
-    if (!(m.meta.push || m.meta.pull)) return false;
+    if (!(m.meta.push || m.meta.pull) || m.meta.bags) return false;
     const size_t want = (m.meta.direct_reply && m.meta.push && m.meta.pull) ? 3 : 2;
     return m.data.size() == want && m.data[0].size() > 0 && (!m.meta.push || m.data[1].size() > 0);
   }
@@ -1108,9 +1150,16 @@ void KVServer<Value>::OnReceive(const Message& msg) {
   CHECK(installed) << "no request handle installed 30 s after the first request";
   stage::Scope t_recv(meta.push ? "server.request.push" : "server.request.pull");
   KVPairs<Value> data;
-  const size_t n = msg.data.size();
+  size_t n = msg.data.size();
   direct_out_ = SVector<Value>();
   direct_taken_ = false;
+  if (msg.meta.bags) {
+    // a pooled request: the bag offsets ride behind the frames every other
+    // request carries, which are parsed below as they always were
+    CHECK_GE(n, (size_t)3) << "a pooled request carries keys, a values frame and its offsets";
+    CHECK(device_frames) << "a pooled request reached a handle that does not take HBM frames";
+    data.offsets = msg.data[--n];
+  }
   if (n && msg.meta.direct_reply && meta.pull) {
     // the last frame is not request data: it is where this Pull's (or
     // PushPull's) values may go — [keys, out] or [keys, vals, out]
@@ -1544,6 +1593,136 @@ int KVWorker<Value>::SendAny(const SVector<Key>& keys, const SVector<Value>* val
                            },
                            true);
   SendBounds(ts, push, true, cmd, kvs, pos, direct, push && direct ? routs.get() : nullptr);
+  return ts;
+}
+
+// The pooled calls (see the class comment).  The request's frames — routed keys,
+// perm, the servers' offsets and, for a Pull, one partial frame per server that
+// owns ids — are held by the completion's captures until it has run.
+template <typename Value>
+int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>* grads,
+                                SVector<Value>* out, bool step, const Callback& cb, int priority) {
+  const bool pull = out != nullptr;
+  const char* who = pull ? "ZPullPooled" : "ZPushPooled";
+  CHECK(default_slicer_) << who << " routes by the servers' key ranges: it cannot be combined with a custom slicer";
+  CHECK(keys.empty() || keys.on_device()) << who << ": keys live in HBM";
+  CHECK(offsets.size() >= 1 && offsets.on_device()) << who << ": offsets are nb + 1 words in HBM";
+  constexpr int dt = device::DType<Value>();
+  CHECK_GE(dt, 0) << who << ": value type not supported by the HBM table";
+  const size_t n = keys.size(), nb = offsets.size() - 1;
+  const SVector<Value>& vals = pull ? *out : *grads;
+  CHECK(vals.empty() || vals.on_device()) << who << ": " << (pull ? "out" : "grads") << " lives in HBM";
+  CHECK_EQ(nb ? vals.size() / nb * nb : (size_t)0, vals.size())
+      << who << ": " << (pull ? "out" : "grads") << " holds a whole number of values per bag";
+  const size_t count = vals.size();  // nb * k
+  const std::vector<Range>& ranges = PostOffice::Get()->GetServerRanges();
+  const size_t ns = ranges.size();
+  const int dev = offsets.device();
+  psg_stream st = device::ThreadStream();
+  // the route, as SendAny's
+  std::vector<uint64_t> pos(ns + 1, 0);
+  SVector<Key> skeys = keys;  // the keys as sent
+  SVector<uint32_t> perm;
+  if (ns == 1 || n == 0) {
+    pos[ns] = n;
+  } else {
+    std::vector<uint64_t> begins(ns), ends(ns);
+    for (size_t i = 0; i < ns; ++i) begins[i] = ranges[i].begin, ends[i] = ranges[i].end;
+    SVector<Key> rkeys = SVector<Key>::OnDevice(n, dev);
+    perm = SVector<uint32_t>::OnDevice(n, dev);
+    int identity = 0;
+    stage::Scope t("worker.route.device", n * sizeof(Key));
+    device::Check(psg_route(keys.data(), n, (int)ns, begins.data(), ends.data(), rkeys.data(), perm.data(), pos.data(),
+                            &identity, st),
+                  "psg_route");
+    if (identity) perm = SVector<uint32_t>();  // already partitioned: the caller's own keys
+    else skeys = rkeys;
+  }
+  // every server's share of every bag; returns once the offsets frame is in
+  // memory (the servers read the frames on streams of their own)
+  SVector<uint64_t> so = SVector<uint64_t>::OnDevice(ns * (nb + 1), dev);
+  {
+    stage::Scope t("worker.route.bags", (ns + 1) * (nb + 1) * sizeof(uint64_t));
+    const int rc = psg_route_bags(offsets.data(), nb, perm.empty() ? nullptr : perm.data(), n, (int)ns, pos.data(),
+                                  so.data(), st);
+    CHECK(rc == PSG_OK) << who << ": " << psg_last_error() << " (nothing was sent)";
+  }
+  if (nb == 0) device::Check(psg_stream_sync(st), "psg_stream_sync");  // (no kernel ran: the route's writes)
+  int owners = 0;
+  for (size_t s = 0; s < ns; ++s) owners += pos[s + 1] != pos[s] ? 1 : 0;
+  const bool direct = pull && detail::DirectReplyOn();
+  // a Pull's partial frames, by server rank; one server: the output itself
+  auto frames = std::make_shared<std::vector<SVector<Value>>>(ns);
+  if (pull)
+    for (size_t s = 0; s < ns; ++s)
+      if (pos[s + 1] != pos[s]) (*frames)[s] = ns == 1 ? *out : SVector<Value>::OnDevice(count, dev);
+  const int ts = customer_->NewRequest(kServerGroup);
+  if (!pull) {
+    AddCallback(ts, [skeys, perm, so, cb]() {
+      if (cb) cb();
+    });
+  } else {
+    const SVector<Value> result = *out;  // shares the caller's buffer
+    AddCallback(ts, [this, ts, skeys, perm, so, frames, result, count, owners, cb]() mutable {
+      std::vector<Reply> kvs;
+      {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = recv_kvs_.find(ts);
+        if (it != recv_kvs_.end()) {
+          kvs.swap(it->second);
+          recv_kvs_.erase(it);
+        }
+      }
+      CHECK_EQ((int)kvs.size(), owners) << "ZPullPooled: lost some servers?";
+      psg_stream s = device::ThreadStream();
+      stage::Scope t("worker.pull.pool_reduce", (owners + 1) * count * sizeof(Value));
+      for (const Reply& r : kvs) {
+        const size_t rank = (size_t)PostOffice::IDToRank(r.sender);
+        CHECK(rank < frames->size() && !(*frames)[rank].empty()) << "ZPullPooled: a reply from a server that was sent nothing";
+        if (r.direct) continue;  // written into the offered frame in place
+        CHECK_EQ(r.kv.vals.size(), count) << "ZPullPooled: a server answers one row per bag";
+        (*frames)[rank] = detail::ToDevice(r.kv.vals, result.device());
+      }
+      std::vector<const void*> parts;  // in rank order
+      for (const auto& f : *frames)
+        if (!f.empty()) parts.push_back(f.data());
+      if (owners == 0) {
+        device::Check(psg_memset(result.data(), 0, count * sizeof(Value), s), "psg_memset");  // every bag is empty: +0
+      } else if (!(parts.size() == 1 && parts[0] == (const void*)result.data())) {
+        device::Check(psg_pool_reduce(result.data(), parts.data(), (int)parts.size(), count, device::DType<Value>(), s),
+                      "psg_pool_reduce");
+      }
+      device::Check(psg_stream_sync(s), "psg_stream_sync");
+      frames.reset();
+      skeys = SVector<Key>();
+      perm = SVector<uint32_t>();
+      so = SVector<uint64_t>();
+      if (cb) cb();
+    });
+  }
+  stage::Scope t_send(pull ? "worker.send.pull" : "worker.send.push");
+  customer_->AddResponse(ts, (int)ns - owners);
+  if (owners == 0) RunCallback(ts);
+  const int cmd = pull ? kRowLookupPooled : step ? kRowUpdatePooledStep : kRowUpdatePooled;
+  for (size_t s = 0; s < ns; ++s) {
+    if (pos[s + 1] == pos[s]) continue;
+    Message msg;
+    msg.meta.app_id = customer_->app_id();
+    msg.meta.customer_id = customer_->customer_id();
+    msg.meta.request = true;
+    msg.meta.push = !pull;
+    msg.meta.pull = pull;
+    msg.meta.head = cmd;
+    msg.meta.timestamp = ts;
+    msg.meta.receiver = PostOffice::ServerRankToID((int)s);
+    msg.meta.priority = priority;
+    msg.meta.direct_reply = direct;
+    msg.meta.bags = true;
+    msg.AddData(skeys.Slice(pos[s], pos[s + 1]));
+    msg.AddData(pull ? (direct ? (*frames)[s] : SVector<Value>()) : *grads);
+    msg.AddData(so.Slice(s * (nb + 1), (s + 1) * (nb + 1)));
+    PostOffice::Get()->van()->Send(msg);
+  }
   return ts;
 }
 

@@ -11,6 +11,7 @@
 //   Pull:  res.vals[i * width + j] = row(key_i)[j]    (post-update)
 //   Pull, cmd kRowLookup:  the same without inserting the keys it has not seen
 //   Push, cmd kRowErase:   keys and no values: the named rows are removed
+//   Pull, cmd kRowLookupPooled:  keys in bags: one row per bag, its rows summed
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first
 // request (or by SaveModel / LoadModel, below); an absent key is inserted with
@@ -42,6 +43,17 @@ namespace ps {
 // A PushPull with either fails the handle's CHECK.
 constexpr int kRowLookup = 3;
 constexpr int kRowErase = 4;
+// The pooled cmds (ps/kv_app.h: kRowLookupPooled = 5, kRowUpdatePooled = 6,
+// kRowUpdatePooledStep = 7), sent by KVWorker::ZPullPooled / ZPushPooled with the
+// request's bag offsets (KVPairs::offsets):
+//   kRowLookupPooled, on a Pull:  psg_table_lookup_pooled on this server's share
+//                           of every bag: nb * width values, one row per bag,
+//                           nothing inserted; all three handles serve it;
+//   kRowUpdatePooled, kRowUpdatePooledStep, on a Push:  keys, offsets and one
+//                           gradient row per bag; KVServerRowOptHandle applies
+//                           them at once (psg_table_update_pooled), the other
+//                           two handles fail a CHECK that says so.
+// A PushPull with any of the three fails the handle's CHECK.
 
 namespace detail {
 
@@ -100,15 +112,70 @@ void ServeRows(const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<
   server->Response(req_meta, res);
 }
 
-// A request with one of the two cmds above, served; false: it is neither.
+// ServeRows for a pooled request (KVPairs::offsets: nb + 1 bag offsets into the
+// keys): a Pull answers nb * width values, into the frame the worker offered
+// when there is one; a Push carries nb * width values.  call(stream, keys,
+// offsets, vals, out, nb) wraps psg_table_lookup_pooled / _update_pooled.
+template <typename Value, typename Call>
+void ServeRowsPooled(const char* who, const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<Value>* server,
+                     size_t width, const char* scope, Call call) {
+  CHECK(!req_data.offsets.empty()) << who << ": cmd " << req_meta.cmd << " needs the bag offsets of a pooled request "
+                                   << "(KVWorker::ZPullPooled / ZPushPooled)";
+  const size_t nb = req_data.offsets.size() - 1;
+  const int dev = PostOffice::Get()->device();
+  if (req_meta.push)
+    CHECK_EQ(nb * width, req_data.vals.size()) << who << ": a pooled Push carries width values per bag";
+  KVPairs<Value> res;
+  SVector<Value> dout;
+  bool direct = false;
+  if (nb) {
+    psg_stream s = device::ThreadStream();
+    SVector<Key> dkeys = ToDeviceAsync(req_data.keys, dev);
+    SVector<uint64_t> doffs = ToDeviceAsync(req_data.offsets, dev);
+    SVector<Value> dvals;
+    if (req_meta.push) dvals = ToDeviceAsync(req_data.vals, dev);
+    if (req_meta.pull) {
+      dout = server->TakeDirectOut(nb * width);
+      direct = !dout.empty();
+      if (!direct) dout = SVector<Value>::OnDevice(nb * width, dev);
+    }
+    stage::Scope t(scope);
+    call(s, dkeys.data(), doffs.data(), dvals.data(), dout.data(), nb);
+  }
+  if (req_meta.pull) {
+    res.keys = req_data.keys;
+    if (!direct) res.vals = req_data.keys.on_device() ? dout : ToHost(dout);
+  }
+  server->Response(req_meta, res);
+}
+
+// The accumulate handle and the sync handle train no row on a pooled gradient:
+// called first, on the host, before the request touches the device.
+inline void RefusePooledUpdate(const char* who, const KVMeta& req_meta) {
+  CHECK(!(req_meta.push && (req_meta.cmd == kRowUpdatePooled || req_meta.cmd == kRowUpdatePooledStep)))
+      << who << ": a pooled update (cmd " << req_meta.cmd << ", KVWorker::ZPushPooled) is served by KVServerRowOptHandle "
+      << "only; this handle does not merge pooled frames";
+}
+
+// A request with kRowLookup, kRowErase or kRowLookupPooled, served; false: it is
+// none of them (the pooled updates are the optimizer handle's own).
 template <typename Value>
 bool ServeRowLifecycle(const char* who, psg_table* table, const KVMeta& req_meta, const KVPairs<Value>& req_data,
                        KVServer<Value>* server, size_t width) {
   const int cmd = req_meta.cmd;
-  if (cmd != kRowLookup && cmd != kRowErase) return false;
+  if (cmd != kRowLookup && cmd != kRowErase && !(cmd >= kRowLookupPooled && cmd <= kRowUpdatePooledStep)) return false;
   CHECK(!(req_meta.push && req_meta.pull))
-      << who << ": a PushPull cannot carry cmd " << cmd << " (kRowLookup goes with a Pull, kRowErase with a Push)";
+      << who << ": a PushPull cannot carry cmd " << cmd
+      << " (kRowLookup and kRowLookupPooled go with a Pull, kRowErase and the pooled updates with a Push)";
   const size_t n = req_data.keys.size();
+  if (req_meta.pull && cmd == kRowLookupPooled) {
+    ServeRowsPooled(who, req_meta, req_data, server, width, "server.handle.rows.lookup_pooled",
+                    [&](psg_stream s, const Key* keys, const uint64_t* offsets, const Value*, Value* out, size_t nb) {
+                      device::Check(psg_table_lookup_pooled(table, keys, offsets, out, n, nb, s),
+                                    "psg_table_lookup_pooled");
+                    });
+    return true;
+  }
   if (req_meta.pull && cmd == kRowLookup) {
     ServeRows(req_meta, req_data, server, width, "server.handle.rows.lookup",
               [&](psg_stream s, const Key* keys, const Value*, Value* out) {
@@ -164,6 +231,7 @@ struct KVServerRowHandle {
     constexpr int dt = device::DType<Value>();
     CHECK_GE(dt, 0) << "KVServerRowHandle: value type not supported by the HBM table";
     CHECK(req_data.lens.empty()) << "KVServerRowHandle: rows have one fixed width, lens are not supported";
+    detail::RefusePooledUpdate("KVServerRowHandle", req_meta);
     detail::EnsureRowTable(&state->table, dt, state->width);
     if (detail::ServeRowLifecycle("KVServerRowHandle", state->table, req_meta, req_data, server, w)) return;
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);

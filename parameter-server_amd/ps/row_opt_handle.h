@@ -20,6 +20,13 @@
 //   Push, cmd 4:       kRowErase — keys and no values: the named rows and their
 //                      moments are removed at once (psg_table_erase); the
 //                      iteration is untouched.  (Both: ps/row_handle.h.)
+//   Pull, cmd 5:       kRowLookupPooled — keys in bags (KVWorker::ZPullPooled):
+//                      one row per bag, the sum of its rows here; no insert.
+//   Push, cmd 6 or 7:  kRowUpdatePooled / kRowUpdatePooledStep — keys in bags and
+//                      one gradient row per bag (KVWorker::ZPushPooled), applied
+//                      at once with the current iteration
+//                      (psg_table_update_pooled); after a cmd 7 from worker 0
+//                      the iteration goes up by one, as after its cmd 1.
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first request
 // (or by SaveModel / LoadModel, which write and read rows, moments and iteration);
@@ -76,6 +83,20 @@ struct KVServerRowOptHandle {
     Table();
     // kRowLookup / kRowErase (ps/row_handle.h): no gradient, no iteration
     if (detail::ServeRowLifecycle("KVServerRowOptHandle", st.table, req_meta, req_data, server, w)) return;
+    if (req_meta.push && (req_meta.cmd == kRowUpdatePooled || req_meta.cmd == kRowUpdatePooledStep)) {
+      // one gradient row per bag, applied at once with the current iteration;
+      // worker 0's kRowUpdatePooledStep ends an iteration, as its cmd 1 does
+      const bool ends = req_meta.cmd == kRowUpdatePooledStep && req_meta.sender == PostOffice::WorkerRankToID(0);
+      detail::ServeRowsPooled("KVServerRowOptHandle", req_meta, req_data, server, w, "server.handle.rows.update_pooled",
+                              [&](psg_stream s, const Key* keys, const uint64_t* offsets, const float* grads, float*,
+                                  size_t nb) {
+                                device::Check(psg_table_update_pooled(st.table, keys, offsets, grads, n, nb, st.lr,
+                                                                      st.iteration, s),
+                                              "psg_table_update_pooled");
+                              });
+      if (ends) ++st.iteration;
+      return;
+    }
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     const bool accumulate = req_meta.push && req_meta.cmd == kAccumulate;
     if (req_meta.push) {

@@ -28,6 +28,10 @@
 //                      moments are removed at once (psg_table_erase); it is not
 //                      held, does not count towards the round and leaves the
 //                      iteration alone.  (Both: ps/row_handle.h.)
+//   Pull, cmd 5:       kRowLookupPooled — keys in bags (KVWorker::ZPullPooled):
+//                      one row per bag, at once; nothing is inserted.
+//   Push, cmd 6 or 7:  the pooled updates fail a CHECK: a round does not merge
+//                      pooled frames (KVServerRowOptHandle applies them).
 //
 // The iteration goes up by one after a round is applied, if the round held
 // worker 0's Push with cmd == 1.  The reference counts when that Push arrives
@@ -97,6 +101,8 @@ struct KVServerRowSyncHandle {
     const int nw = PostOffice::Get()->num_workers();
     CHECK(nw <= kMaxWorkers) << "KVServerRowSyncHandle: a round merges at most " << kMaxWorkers << " workers, the job has "
                              << nw;
+    // a pooled gradient frame cannot join a round: refused before anything else
+    detail::RefusePooledUpdate("KVServerRowSyncHandle", req_meta);
     Table();
     // kRowLookup / kRowErase (ps/row_handle.h): at once, as cmd 2; neither joins a round
     if (detail::ServeRowLifecycle("KVServerRowSyncHandle", st.table, req_meta, req_data, server, w)) return;

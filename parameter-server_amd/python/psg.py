@@ -53,7 +53,7 @@ EXPORTS = [
     "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
-    "psg_route", "psg_rows_gather", "psg_rows_scatter",
+    "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
     "psg_comm_push_pull", "psg_comm_push_keyed", "psg_comm_pull_keyed",
@@ -176,6 +176,8 @@ def lib() -> C.CDLL:
             "psg_route": ([vp, u64, i32, vp, vp, vp, vp, vp, C.POINTER(i32), vp], i32),
             "psg_rows_gather": ([vp, vp, vp, u64, u64, vp], i32),
             "psg_rows_scatter": ([vp, vp, vp, u64, u64, vp], i32),
+            "psg_route_bags": ([vp, u64, vp, u64, i32, vp, vp, vp], i32),
+            "psg_pool_reduce": ([vp, C.POINTER(vp), i32, u64, i32, vp], i32),
             "psg_comm_id_bytes": ([], i32), "psg_comm_get_id": ([vp], i32),
             "psg_comm_bucket_plan": ([u64, i32, vp, vp, i32, C.POINTER(i32)], i32),
             "psg_comm_sync": ([vp, vp, f64], i32), "psg_comm_abort": ([vp], i32),
@@ -699,6 +701,24 @@ def rows_gather(dst, src, perm, n: int, row_bytes: int, stream=None) -> None:
 def rows_scatter(dst, src, perm, n: int, row_bytes: int, stream=None) -> None:
     """dst row perm[r] = src row r for r < n (stream-ordered)."""
     _call("psg_rows_scatter", _ptr(dst), _ptr(src), _ptr(perm), n, row_bytes, _s(stream))
+
+
+def route_bags(offsets, nb: int, perm, n: int, key_pos: np.ndarray, server_offsets, stream=None) -> None:
+    """Every server's share of every bag of a routed list (psg_route_bags):
+    server_offsets (device, ns * (nb + 1) uint64) gets, for server s, the nb + 1
+    offsets of its stretch; perm is psg_route's, or None for a list it left in
+    place (identity); key_pos its ns + 1 bounds.  Returns once they are written."""
+    kp = np.ascontiguousarray(key_pos, dtype=np.uint64)
+    _call("psg_route_bags", _ptr(offsets), nb, _ptr(perm), n, len(kp) - 1, kp.ctypes.data_as(C.c_void_p),
+          _ptr(server_offsets), _s(stream))
+
+
+def pool_reduce(out, partials, count: int, dtype: int, stream=None) -> None:
+    """out[i] = the servers' pooled partials[s][i] added in list order from +0
+    (psg_pool_reduce); count elements of `dtype` each; stream-ordered."""
+    k = len(partials)
+    arr = (C.c_void_p * max(k, 1))(*[_ptr(p) for p in partials])
+    _call("psg_pool_reduce", _ptr(out), arr, k, count, dtype, _s(stream))
 
 
 def merge(segments, elem_size: int, dst, dst_count: int, stream=None) -> None:
