@@ -28,6 +28,8 @@
  *                    ids in bags, one row per bag: the bag's rows summed, and
  *                    that round with the bag's gradient row for each of its ids
  *                    (no pooling in the reference)
+ *   psg_table_update_pooled_merged
+ *                    the sync-mode round over k frames, pooled or plain
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
  *   psg_slice        KVWorker<V>::DefaultSlicer           src/ps/KVApp.h:515-574
  *   psg_merge        the AddPullCB merge lambda           src/ps/KVApp.h:673-726
@@ -739,6 +741,51 @@ int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* 
 int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets,
                             const float* grads, uint64_t n, uint64_t nb, float lr, int iteration,
                             psg_stream stream);
+/* One sync-mode round whose frames may be pooled: psg_table_update_merged's
+ * Push with psg_table_update_pooled's gradient rows.  The five *_host arguments
+ * are host arrays of k entries, 1 <= k <= 16; keys_host, offsets_host and
+ * grads_host hold DEVICE pointers.  Frame j has ns_host[j] keys and is
+ *   pooled, offsets_host[j] != NULL:  offsets_j holds nbs_host[j] + 1 words under
+ *           the three rules of psg_table_lookup_pooled, grads_j nbs_host[j] * width
+ *           floats, one row per bag;
+ *   plain,  offsets_host[j] == NULL:  grads_j holds ns_host[j] * width floats, one
+ *           row per key; nbs_host[j] is ignored.
+ * Keys come in any order and may repeat, inside bags, across bags and across
+ * frames; a frame may be empty.  Keys, rows, Adam moments and size end, bit for
+ * bit, as after
+ *   psg_table_update_merged(t, PSG_PUSH, k, keys_host, ns_host, E, NULL, lr,
+ *                           iteration, stream, NULL)
+ * with E_j = grads_j for a plain frame and E_j[i*width + c] =
+ * grads_j[bag_j(i)*width + c] for a pooled one; no E_j is ever built.  Per id the
+ * gradient rows of all its occurrences are summed from +0.0f in arrival order
+ * (frame 0 .. k-1, then position), one f32 add each, then the optimizer steps
+ * ONCE.  An absent id is inserted once with a zero row and zero moments, then
+ * updated.  An empty bag's gradient row is never read.  Push only: there is no
+ * reply.
+ * Refused before any device call, in this order: PSG_ERR_INVALID for a null
+ * table; k outside [1, 16]; iteration < 0; any of the five host arrays null;
+ * then per frame in order: null keys with ns[j] > 0, and for a pooled frame null
+ * grads with nbs[j] > 0 or nbs[j] == 0 with ns[j] > 0, for a plain frame null
+ * grads with ns[j] > 0.  PSG_ERR_RANGE: sum(ns) above 2^32 - 2, or the gradient
+ * rows of all frames (ns[j] of a plain frame, nbs[j] of a pooled one) above
+ * 2^32 - 2.  PSG_ERR_UNSUPPORTED: a table that is not F32.  sum(ns) == 0 with
+ * valid offsets is a no-op.
+ * Found on the device, with nothing written: the offsets of a pooled frame with
+ * nbs[j] > 0 break a rule -> PSG_ERR_INVALID; a key of any frame outside the
+ * table's range -> PSG_ERR_RANGE; both -> PSG_ERR_INVALID; keys, rows, moments,
+ * size and capacity stay bit for bit unchanged.  Every offsets array is checked
+ * before anything else reads it.  Returns as psg_table_update_merged: keys,
+ * offsets and grads are no longer read.
+ * *path_host (may be NULL): all frames plain — the round IS
+ * psg_table_update_merged's and reports its path; k == 1 and pooled — it is
+ * psg_table_update_pooled's, PSG_MERGED_SAME_LIST for a strictly ascending list,
+ * else PSG_MERGED_SORTED; otherwise PSG_MERGED_SORTED: the lists are sorted as
+ * one with, per occurrence, the index of its gradient row in the frames'
+ * gradient arrays laid end to end.  0 where nothing was served. */
+int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys_host,
+                                   const uint64_t* ns_host, const uint64_t* const* offsets_host,
+                                   const uint64_t* nbs_host, const float* const* grads_host,
+                                   float lr, int iteration, psg_stream stream, int* path_host);
 
 /* ======================================================================== */
 /* Worker side: key-range slicing and pull merge                              */

@@ -72,6 +72,13 @@
 // is the merged round's front half on one list with the bag's gradient row in
 // every occurrence's place (k_bag_of, k_rows_walk_pool).  k_offsets_check runs
 // in front of either, and nothing walks an offsets array it refused.
+//
+// The round of pooled and plain frames (psg_table_update_pooled_merged) is the
+// merged round's sorted path with the pooled update's payload: the k key lists
+// sorted as one with, per occurrence, the index of its gradient row in the
+// frames' gradient arrays laid end to end (k_bag_of / k_row_index from each
+// frame's first row), and k_rows_walk_pool picking the frame's array with
+// frame_of, as k_rows_walk_merge does.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1011,15 +1018,16 @@ __global__ __launch_bounds__(256) void k_rows_walk_merge(typename UNIT::U* __res
 }
 
 // ---- the pooled update (psg_table_update_pooled) ------------------------------------
-// bag_of[i] for every position i < n of the id list: the bag b with
+// base + bag_of[i] for every position i < n of the id list: the bag b with
 // offsets[b] <= i < offsets[b + 1] (offsets checked: k_offsets_check).  A block
 // takes kBlock bags, keeps their kBlock + 1 offsets in LDS and writes the
 // stretch of positions they cover, consecutive lanes consecutive words; a lane
 // finds its position's bag in 8 steps over LDS (the last offset <= i: empty bags
 // share an offset with the bag behind them and own no position).  8 B read per
 // bag, 4 B written per id — and a per-occurrence search of `offsets` in global
-// memory is kept out of the walk's gradient chain.
-__global__ __launch_bounds__(256) void k_bag_of(const uint64_t* __restrict__ offsets, uint64_t nb,
+// memory is kept out of the walk's gradient chain.  base: 0, or the first
+// gradient row of the list's frame in a round of several (k_row_index).
+__global__ __launch_bounds__(256) void k_bag_of(const uint64_t* __restrict__ offsets, uint64_t nb, uint32_t base,
                                                 uint32_t* __restrict__ bag_of) {
   __shared__ uint32_t off[kBlock + 1];
   const uint64_t ntiles = (nb + kBlock - 1) / kBlock;
@@ -1036,31 +1044,64 @@ __global__ __launch_bounds__(256) void k_bag_of(const uint64_t* __restrict__ off
         if (off[mid] <= p) lo = mid;
         else hi = mid;
       }
-      bag_of[p] = (uint32_t)(b0 + lo);
+      bag_of[p] = base + (uint32_t)(b0 + lo);
     }
     __syncthreads();
   }
 }
 
-// Pass 2 of psg_table_update_pooled: k_rows_walk_merge's walk on ONE gradient
-// array with a row per bag.  Unique row u (slot slots[u]) for u < m; its
+// What k_bag_of writes for a pooled frame, for a plain one (a gradient row per
+// key): idx[i] = base + i for i < n.
+__global__ __launch_bounds__(256) void k_row_index(uint32_t* __restrict__ idx, uint64_t n, uint32_t base) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+    idx[i] = base + (uint32_t)i;
+}
+
+// Where the pooled walk finds gradient row `row`.  OneArray: in the one array of
+// psg_table_update_pooled, a row per bag.  FrameArrays: in the frame that holds
+// row `row` of the round's gradient arrays laid end to end
+// (psg_table_update_pooled_merged): f.off[j] is the first row of frame j,
+// f.vals[j] its array moved back by that many rows, so `row` indexes it as it is;
+// a block keeps the addresses in LDS, as k_rows_walk_merge does.
+template <typename U> struct OneArray {
+  static constexpr bool kFrames = false;
+  const U* grads;
+};
+struct FrameArrays {
+  static constexpr bool kFrames = true;
+  Frames f;
+};
+
+// Pass 2 of the pooled updates: k_rows_walk_merge's walk with a gradient-row
+// index per occurrence.  Unique row u (slot slots[u]) for u < m; its
 // occurrences are the sorted positions seg[u] .. seg[u + 1), in arrival order,
-// and bags[p] is the bag of the occurrence at sorted position p — the sort
-// carried bag_of as its payload, so bags IS bag_of[perm[.]] and the chain is
-// bags -> gradient -> add, as the merged walk's is perm -> gradient -> add: the
-// bag two ahead and the gradient unit one ahead are loaded before the current
-// add.  The sum starts from +0.0f, then one step and one store: one writer per
-// row, no atomics.  No Frames, no frame_of, no LDS, no Pull leg.  STRICT: the
-// list ascends strictly, nothing was sorted; row u's one occurrence is position
-// u, bags is bag_of itself and seg is not read.
-template <typename UNIT, bool STRICT>
+// and bags[p] is the gradient row of the occurrence at sorted position p — the
+// sort carried it as its payload (k_bag_of, k_row_index), so bags IS
+// bag_of[perm[.]] and the chain is bags -> gradient -> add, as the merged walk's
+// is perm -> gradient -> add: the row index two ahead and the gradient unit one
+// ahead are loaded before the current add.  The sum starts from +0.0f, then one
+// step and one store: one writer per row, no atomics, no Pull leg.  SRC says
+// where a gradient row lives: OneArray (no Frames, no frame_of, no LDS) or
+// FrameArrays (frame_of over the frames' first rows: 15 compares and one 8-B
+// LDS read an occurrence).  STRICT (OneArray only): the list ascends strictly,
+// nothing was sorted; row u's one occurrence is position u, bags is bag_of
+// itself and seg is not read.
+template <typename UNIT, typename SRC, bool STRICT>
 __global__ __launch_bounds__(256) void k_rows_walk_pool(typename UNIT::U* __restrict__ R, double* __restrict__ M,
                                                         const uint32_t* __restrict__ slots,
                                                         const uint32_t* __restrict__ seg,
-                                                        const uint32_t* __restrict__ bags,
-                                                        const typename UNIT::U* __restrict__ grads, uint64_t m,
+                                                        const uint32_t* __restrict__ bags, SRC src, uint64_t m,
                                                         uint32_t upr, uint32_t rpt, typename UNIT::Params prm) {
   using U = typename UNIT::U;
+  static_assert(!(STRICT && SRC::kFrames), "a round of several frames is always sorted");
+  __shared__ uint64_t vals_at[kMaxFrames];  // FrameArrays only
+  if constexpr (SRC::kFrames) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int j = 0; j < kMaxFrames; ++j) vals_at[j] = (uint64_t)src.f.vals[j];
+    }
+    __syncthreads();
+  }
   const uint64_t ntiles = (m + rpt - 1) / rpt;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const uint64_t u0 = t * rpt;
@@ -1072,16 +1113,22 @@ __global__ __launch_bounds__(256) void k_rows_walk_pool(typename UNIT::U* __rest
       const uint32_t c = w.c;
       const uint32_t p0 = STRICT ? (uint32_t)u : seg[u];
       const uint32_t pe = STRICT ? (uint32_t)u + 1 : seg[u + 1];  // > p0: every unique key has an occurrence
+      auto grad_at = [&](uint32_t row) {
+        if constexpr (SRC::kFrames)
+          return UNIT::load_grad((const U*)vals_at[frame_of(src.f, row)], (uint64_t)row * upr + c);
+        else
+          return UNIT::load_grad(src.grads, (uint64_t)row * upr + c);
+      };
       UNIT x;
       x.locate(slots[u], c, upr, prm);
       x.load_state(R, M, prm);  // issued here, used after the sum
       uint32_t b1 = p0 + 1 < pe ? bags[p0 + 1] : 0;
-      U v = UNIT::load_grad(grads, (uint64_t)bags[p0] * upr + c);
+      U v = grad_at(bags[p0]);
       U s = {};  // +0.0f
       for (uint32_t p = p0; p < pe; ++p) {
         const uint32_t b2 = p + 2 < pe ? bags[p + 2] : 0;
         U vn = v;
-        if (p + 1 < pe) vn = UNIT::load_grad(grads, (uint64_t)b1 * upr + c);
+        if (p + 1 < pe) vn = grad_at(b1);
         s = s + v;
         b1 = b2, v = vn;
       }
@@ -1842,36 +1889,44 @@ int lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, v
   return require_in_range(t);
 }
 
+// The pooled walk for one unit type: over the plan's unique rows, their gradient
+// rows in the one array `grads` or (f not null, always with a plan) in the
+// round's frames; without a plan the strict walk over the list's n rows.
 template <typename UNIT>
-int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, const float* grads, uint64_t n,
-                     uint32_t upr, const typename UNIT::Params& prm, hipStream_t st) {
+int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, const float* grads, const Frames* f,
+                     uint64_t n, uint32_t upr, const typename UNIT::Params& prm, hipStream_t st) {
   using U = typename UNIT::U;
   const uint32_t rpt = rows_per_tile(upr);
   const uint64_t rows = p ? p->m : n;
   const unsigned g = grid_for((rows + rpt - 1) / rpt);
-  if (p)
-    k_rows_walk_pool<UNIT, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, (const U*)grads,
-                                                        rows, upr, rpt, prm);
+  const OneArray<U> one = {(const U*)grads};
+  if (f)
+    k_rows_walk_pool<UNIT, FrameArrays, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm,
+                                                                     FrameArrays{*f}, rows, upr, rpt, prm);
+  else if (p)
+    k_rows_walk_pool<UNIT, OneArray<U>, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, one,
+                                                                     rows, upr, rpt, prm);
   else
-    k_rows_walk_pool<UNIT, true><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, nullptr, bag_of, (const U*)grads,
-                                                       rows, upr, rpt, prm);
+    k_rows_walk_pool<UNIT, OneArray<U>, true><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, nullptr, bag_of, one,
+                                                                    rows, upr, rpt, prm);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
 
+// vec: 16-B units (optimize_vec's condition for a Push, on every gradient array)
 template <bool ADAM>
-int pooled_adam(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, const float* grads, uint64_t n, float lr,
-                int iteration, hipStream_t st) {
-  if (optimize_vec(t, PSG_PUSH, grads, nullptr))
-    return launch_walk_pool<OptUnit<ADAM, true>>(t, p, bag_of, grads, n, t->width / 4,
+int pooled_adam(psg_table* t, bool vec, const AnyPlan* p, const uint32_t* bag_of, const float* grads, const Frames* f,
+                uint64_t n, float lr, int iteration, hipStream_t st) {
+  if (vec)
+    return launch_walk_pool<OptUnit<ADAM, true>>(t, p, bag_of, grads, f, n, t->width / 4,
                                                  {t->width, lr, adam_args(t, iteration)}, st);
-  return launch_walk_pool<OptUnit<ADAM, false>>(t, p, bag_of, grads, n, t->width,
+  return launch_walk_pool<OptUnit<ADAM, false>>(t, p, bag_of, grads, f, n, t->width,
                                                 {t->width, lr, adam_args(t, iteration)}, st);
 }
 
-int update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads, uint64_t n,
-                  uint64_t nb, float lr, int iteration, psg_stream stream) {
-  const char* name = "psg_table_update_pooled";
+// path (may be null): how the list was served, as psg_table_update_merged reports it
+int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads,
+                  uint64_t n, uint64_t nb, float lr, int iteration, psg_stream stream, int* path) {
   PSG_TRY(pooled_args(name, t, keys, offsets, grads, "grads", n, nb));
   PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
   PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
@@ -1898,7 +1953,7 @@ int update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, c
   const bool strict = !t->flags_host[R_UNSORTED];  // as PSG_MERGED_SAME_LIST is decided for k = 1
   AnyScratch a;
   PSG_TRY(any_scratch(t, n, &a));
-  k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, a.p0);
+  k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, 0, a.p0);
   PSG_HIP(hipGetLastError());
   AnyPlan plan;
   const AnyPlan* p = nullptr;
@@ -1909,10 +1964,107 @@ int update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, c
     PSG_TRY(plan_scratch(t, a, n, &plan, st, true));
     p = &plan;
   }
-  PSG_TRY(t->adam ? pooled_adam<true>(t, p, a.p0, grads, n, lr, iteration, st)
-                  : pooled_adam<false>(t, p, a.p0, grads, n, lr, iteration, st));
+  const bool vec = optimize_vec(t, PSG_PUSH, grads, nullptr);
+  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, p, a.p0, grads, nullptr, n, lr, iteration, st)
+                  : pooled_adam<false>(t, vec, p, a.p0, grads, nullptr, n, lr, iteration, st));
   // complete on return: keys, offsets and grads no longer read
   PSG_HIP(hipStreamSynchronize(st));
+  if (path) *path = strict ? PSG_MERGED_SAME_LIST : PSG_MERGED_SORTED;
+  return PSG_OK;
+}
+
+// ---- the round of pooled and plain frames (psg_table_update_pooled_merged) ---------
+// update_merged's sorted path with update_pooled's payload: the k key lists one
+// behind the other in the sort's key buffer and, in its payload buffer, every
+// occurrence's gradient row in the frames' gradient arrays laid end to end
+// (k_row_index for a plain frame, k_bag_of for a pooled one, each from its
+// frame's first row).  A round of plain frames is update_merged's, one pooled
+// frame is update_pooled's.
+int update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys, const uint64_t* ns,
+                         const uint64_t* const* offsets, const uint64_t* nbs, const float* const* grads, float lr,
+                         int iteration, psg_stream stream, int* path_host) {
+  const char* name = "psg_table_update_pooled_merged";
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  PSG_REQUIRE(k >= 1 && k <= kMaxFrames, PSG_ERR_INVALID, "%s: %d frames outside [1, %d]", name, k, kMaxFrames);
+  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
+  PSG_REQUIRE(keys && ns && offsets && nbs && grads, PSG_ERR_INVALID, "%s: null keys, ns, offsets, nbs or grads array",
+              name);
+  bool pooled = false;
+  for (int j = 0; j < k; ++j) {
+    PSG_REQUIRE(keys[j] || ns[j] == 0, PSG_ERR_INVALID, "%s: null keys of frame %d", name, j);
+    if (offsets[j]) {
+      pooled = true;
+      PSG_REQUIRE(grads[j] || nbs[j] == 0, PSG_ERR_INVALID, "%s: null grads of pooled frame %d", name, j);
+      PSG_REQUIRE(nbs[j] > 0 || ns[j] == 0, PSG_ERR_INVALID, "%s: %llu keys of frame %d and no bag to hold them", name,
+                  (unsigned long long)ns[j], j);
+    } else {
+      PSG_REQUIRE(grads[j] || ns[j] == 0, PSG_ERR_INVALID, "%s: null grads of frame %d", name, j);
+    }
+  }
+  Frames f = {};  // off: the first gradient row of each frame
+  f.k = k;
+  uint32_t koff[kMaxFrames];  // the first key of each frame in the concatenation
+  uint64_t N = 0, G = 0;
+  for (int j = 0; j < k; ++j) {
+    const uint64_t g = offsets[j] ? nbs[j] : ns[j];
+    PSG_REQUIRE(ns[j] <= kMaxRows && N + ns[j] <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one round", name);
+    PSG_REQUIRE(g <= kMaxRows && G + g <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 gradient rows in one round",
+                name);
+    koff[j] = (uint32_t)N;
+    f.off[j] = (uint32_t)G;
+    N += ns[j];
+    G += g;
+  }
+  for (int j = k; j <= kMaxFrames; ++j) f.off[j] = 0xffffffffu;
+  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
+  if (path_host) *path_host = 0;
+  if (!pooled) return update_merged(t, PSG_PUSH, k, keys, ns, grads, nullptr, lr, iteration, stream, path_host);
+  if (k == 1) return update_pooled(name, t, keys[0], offsets[0], grads[0], ns[0], nbs[0], lr, iteration, stream, path_host);
+  if (N == 0 && G == 0) return PSG_OK;  // no key and no bag: nothing to check either
+  hipStream_t st = (hipStream_t)stream;
+  // the front half: every offsets array checked before anything else reads it,
+  // every key against the range; one synchronisation, nothing written yet
+  AnyScratch a = {};
+  if (N) {
+    PSG_TRY(ensure_slots(t, N));
+    PSG_TRY(any_scratch(t, N, &a));
+  }
+  memset(t->flags_host, 0, kNFlags * sizeof(int));
+  for (int j = 0; j < k; ++j) {
+    if (offsets[j] && nbs[j]) PSG_TRY(launch_offsets_check(offsets[j], ns[j], nbs[j], t->flags, st));
+    if (ns[j]) PSG_HIP(hipMemcpyAsync(a.k0 + koff[j], keys[j], ns[j] * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  }
+  if (N) {
+    k_rows_resolve<<<grid_for((N + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(a.k0, N, t->keys, t->size, t->key_begin,
+                                                                              t->key_end, t->slots, t->flags);
+    PSG_HIP(hipGetLastError());
+  }
+  PSG_HIP(hipStreamSynchronize(st));
+  PSG_REQUIRE(!t->flags_host[R_OFFSETS], PSG_ERR_INVALID,
+              "%s: the offsets of a pooled frame do not start at 0, ascend and end at its ns", name);
+  PSG_TRY(require_in_range(t));
+  if (N == 0) return PSG_OK;  // every frame is empty: no gradient row is read
+  // the payload, and each frame's array moved back by its first row; 16-B units
+  // under optimize_vec's condition on every array that is read
+  bool vec = t->width % 4 == 0;
+  const uint64_t row_bytes = (uint64_t)t->width * sizeof(float);
+  for (int j = 0; j < k; ++j) {
+    if (ns[j] == 0) continue;
+    if (offsets[j])
+      k_bag_of<<<grid_for((nbs[j] + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets[j], nbs[j], f.off[j], a.p0 + koff[j]);
+    else
+      k_row_index<<<grid_for((ns[j] + kBlock - 1) / kBlock), kBlock, 0, st>>>(a.p0 + koff[j], ns[j], f.off[j]);
+    PSG_HIP(hipGetLastError());
+    vec = vec && aligned16(grads[j]);
+    f.vals[j] = (const void*)((uintptr_t)grads[j] - f.off[j] * row_bytes);
+  }
+  AnyPlan plan;
+  PSG_TRY(plan_scratch(t, a, N, &plan, st, true));
+  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, &plan, nullptr, nullptr, &f, N, lr, iteration, st)
+                  : pooled_adam<false>(t, vec, &plan, nullptr, nullptr, &f, N, lr, iteration, st));
+  // complete on return: keys, offsets and grads no longer read
+  PSG_HIP(hipStreamSynchronize(st));
+  if (path_host) *path_host = PSG_MERGED_SORTED;
   return PSG_OK;
 }
 
@@ -2087,7 +2239,15 @@ int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* 
 
 int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads,
                             uint64_t n, uint64_t nb, float lr, int iteration, psg_stream stream) {
-  return update_pooled(t, keys, offsets, grads, n, nb, lr, iteration, stream);
+  return update_pooled("psg_table_update_pooled", t, keys, offsets, grads, n, nb, lr, iteration, stream, nullptr);
+}
+
+int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys_host, const uint64_t* ns_host,
+                                   const uint64_t* const* offsets_host, const uint64_t* nbs_host,
+                                   const float* const* grads_host, float lr, int iteration, psg_stream stream,
+                                   int* path_host) {
+  return update_pooled_merged(t, k, keys_host, ns_host, offsets_host, nbs_host, grads_host, lr, iteration, stream,
+                              path_host);
 }
 
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {

@@ -449,16 +449,30 @@ class KVWorker : public SimpleApp {
    * ZPushPooled: grads holds nb * k values, one gradient row per bag; every
    *   server gets the whole frame.  step: the update also ends worker 0's
    *   iteration on the servers it reaches, as a Push with cmd 1 does.
+   * ZPushPooledAll: ZPushPooled with one difference: EVERY server is sent a
+   *   message.  A server that owns none of the ids gets zero keys, its nb + 1
+   *   offsets (psg_route_bags writes them for it: all zero) and the gradient
+   *   frame.  It is the call of a sync job (KVServerRowSyncHandle): a server
+   *   closes its round when num_workers() gradient Pushes are held, so in a sync
+   *   job every worker's Push must reach every server — the rule the plain
+   *   calls have as well (ZPushAny sends nothing to a server that owns no key of
+   *   the list: there a worker's list has to reach every server).  ZPushPooled
+   *   skips the servers that own none of a list's ids, and their rounds would
+   *   wait for ever.
    * CHECKs: no custom slicer; out / grads hold a multiple of nb values;
    * psg_route_bags did not refuse the offsets (nothing is sent then). */
   int ZPullPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, SVector<Value>* out,
                   const Callback& cb = nullptr, int priority = 0) {
     CHECK_NOTNULL(out);
-    return SendPooled(keys, offsets, nullptr, out, false, cb, priority);
+    return SendPooled(keys, offsets, nullptr, out, false, false, cb, priority);
   }
   int ZPushPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>& grads,
                   bool step = false, const Callback& cb = nullptr, int priority = 0) {
-    return SendPooled(keys, offsets, &grads, nullptr, step, cb, priority);
+    return SendPooled(keys, offsets, &grads, nullptr, step, false, cb, priority);
+  }
+  int ZPushPooledAll(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>& grads,
+                     bool step = false, const Callback& cb = nullptr, int priority = 0) {
+    return SendPooled(keys, offsets, &grads, nullptr, step, true, cb, priority);
   }
   /* Host-vector forms: the same routing done on the host (a stable counting
    * pass over the owners), the routed copies sent as host frames on its bounds,
@@ -565,9 +579,10 @@ class KVWorker : public SimpleApp {
               int priority);
   int SendAnyHost(const std::vector<Key>& keys, const std::vector<Value>* vals, std::vector<Value>* outs, int cmd,
                   const Callback& cb, int priority);
-  /* ZPullPooled (grads == nullptr) and ZPushPooled (out == nullptr) */
+  /* ZPullPooled (grads == nullptr) and ZPushPooled / ZPushPooledAll (out ==
+   * nullptr; all: also the servers that own none of the ids are sent to) */
   int SendPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>* grads,
-                 SVector<Value>* out, bool step, const Callback& cb, int priority);
+                 SVector<Value>* out, bool step, bool all, const Callback& cb, int priority);
   void OnReceive(const Message& msg) override;
   void DefaultSlicer(Data& send, const std::vector<Range>& ranges, SlicedKVs* sliced);
   /* routed: the request went out on SendBounds — its keys are partitioned by
@@ -1601,9 +1616,10 @@ int KVWorker<Value>::SendAny(const SVector<Key>& keys, const SVector<Value>* val
 // owns ids — are held by the completion's captures until it has run.
 template <typename Value>
 int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>* grads,
-                                SVector<Value>* out, bool step, const Callback& cb, int priority) {
+                                SVector<Value>* out, bool step, bool all, const Callback& cb, int priority) {
   const bool pull = out != nullptr;
-  const char* who = pull ? "ZPullPooled" : "ZPushPooled";
+  const char* who = pull ? "ZPullPooled" : all ? "ZPushPooledAll" : "ZPushPooled";
+  CHECK(!(pull && all)) << "ZPullPooled asks the servers that own ids";
   CHECK(default_slicer_) << who << " routes by the servers' key ranges: it cannot be combined with a custom slicer";
   CHECK(keys.empty() || keys.on_device()) << who << ": keys live in HBM";
   CHECK(offsets.size() >= 1 && offsets.on_device()) << who << ": offsets are nb + 1 words in HBM";
@@ -1648,8 +1664,9 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
     CHECK(rc == PSG_OK) << who << ": " << psg_last_error() << " (nothing was sent)";
   }
   if (nb == 0) device::Check(psg_stream_sync(st), "psg_stream_sync");  // (no kernel ran: the route's writes)
+  // the servers that are sent to: those that own ids, or (all) every one
   int owners = 0;
-  for (size_t s = 0; s < ns; ++s) owners += pos[s + 1] != pos[s] ? 1 : 0;
+  for (size_t s = 0; s < ns; ++s) owners += all || pos[s + 1] != pos[s] ? 1 : 0;
   const bool direct = pull && detail::DirectReplyOn();
   // a Pull's partial frames, by server rank; one server: the output itself
   auto frames = std::make_shared<std::vector<SVector<Value>>>(ns);
@@ -1705,7 +1722,7 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
   if (owners == 0) RunCallback(ts);
   const int cmd = pull ? kRowLookupPooled : step ? kRowUpdatePooledStep : kRowUpdatePooled;
   for (size_t s = 0; s < ns; ++s) {
-    if (pos[s + 1] == pos[s]) continue;
+    if (!all && pos[s + 1] == pos[s]) continue;
     Message msg;
     msg.meta.app_id = customer_->app_id();
     msg.meta.customer_id = customer_->customer_id();

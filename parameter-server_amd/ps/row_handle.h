@@ -51,8 +51,10 @@ constexpr int kRowErase = 4;
 //                           nothing inserted; all three handles serve it;
 //   kRowUpdatePooled, kRowUpdatePooledStep, on a Push:  keys, offsets and one
 //                           gradient row per bag; KVServerRowOptHandle applies
-//                           them at once (psg_table_update_pooled), the other
-//                           two handles fail a CHECK that says so.
+//                           them at once (psg_table_update_pooled),
+//                           KVServerRowSyncHandle holds them for its round
+//                           (psg_table_update_pooled_merged), KVServerRowHandle
+//                           fails a CHECK that says so.
 // A PushPull with any of the three fails the handle's CHECK.
 
 namespace detail {
@@ -149,8 +151,8 @@ void ServeRowsPooled(const char* who, const KVMeta& req_meta, const KVPairs<Valu
   server->Response(req_meta, res);
 }
 
-// The accumulate handle and the sync handle train no row on a pooled gradient:
-// called first, on the host, before the request touches the device.
+// The accumulate handle trains no row on a pooled gradient: called first, on
+// the host, before the request touches the device.
 inline void RefusePooledUpdate(const char* who, const KVMeta& req_meta) {
   CHECK(!(req_meta.push && (req_meta.cmd == kRowUpdatePooled || req_meta.cmd == kRowUpdatePooledStep)))
       << who << ": a pooled update (cmd " << req_meta.cmd << ", KVWorker::ZPushPooled) is served by KVServerRowOptHandle "

@@ -30,11 +30,21 @@
 //                      iteration alone.  (Both: ps/row_handle.h.)
 //   Pull, cmd 5:       kRowLookupPooled — keys in bags (KVWorker::ZPullPooled):
 //                      one row per bag, at once; nothing is inserted.
-//   Push, cmd 6 or 7:  the pooled updates fail a CHECK: a round does not merge
-//                      pooled frames (KVServerRowOptHandle applies them).
+//   Push, cmd 6 or 7:  kRowUpdatePooled / kRowUpdatePooledStep — keys in bags and
+//                      one gradient row per bag (KVWorker::ZPushPooledAll).  Staged
+//                      with its offsets and held; it counts towards the round as
+//                      a cmd 0 / 1 Push does, also with no key of this server's
+//                      in it.  A round that holds one is served by ONE
+//                      psg_table_update_pooled_merged call over pooled and plain
+//                      frames alike (the bag's gradient row stands for every id
+//                      of the bag; no expanded frame is ever built); then every
+//                      held plain PushPull is answered with a Pull of its keys
+//                      (psg_table_handle_any): the updated row for every
+//                      occurrence, the bytes psg_table_update_merged's Pull leg
+//                      gives.  A round without one is exactly the call above.
 //
 // The iteration goes up by one after a round is applied, if the round held
-// worker 0's Push with cmd == 1.  The reference counts when that Push arrives
+// worker 0's Push with cmd == 1 or kRowUpdatePooledStep.  The reference counts when that Push arrives
 // (LRServer.h:193-195), so whether the round it closes or the next one sees the
 // new count depends on arrival order; counting after the round is the order
 // "worker 0 arrives last", and a round's result does not depend on arrival.
@@ -68,6 +78,10 @@ struct KVServerRowSyncHandle {
     SVector<float> dvals;
     SVector<float> dout;   // a PushPull's reply: the worker's own slice (direct) or ours
     bool direct = false;
+    bool pooled = false;         // cmd kRowUpdatePooled / kRowUpdatePooledStep: vals hold one row per bag
+    SVector<uint64_t> offsets;   // its nb + 1 bag offsets, as received
+    SVector<uint64_t> doffsets;  // in HBM
+    size_t nb = 0;
   };
   struct State {
     psg_table* table = nullptr;
@@ -101,12 +115,16 @@ struct KVServerRowSyncHandle {
     const int nw = PostOffice::Get()->num_workers();
     CHECK(nw <= kMaxWorkers) << "KVServerRowSyncHandle: a round merges at most " << kMaxWorkers << " workers, the job has "
                              << nw;
-    // a pooled gradient frame cannot join a round: refused before anything else
-    detail::RefusePooledUpdate("KVServerRowSyncHandle", req_meta);
     Table();
     // kRowLookup / kRowErase (ps/row_handle.h): at once, as cmd 2; neither joins a round
     if (detail::ServeRowLifecycle("KVServerRowSyncHandle", st.table, req_meta, req_data, server, w)) return;
-    if (req_meta.push) {
+    const bool pooled = req_meta.push && (req_meta.cmd == kRowUpdatePooled || req_meta.cmd == kRowUpdatePooledStep);
+    if (pooled) {
+      CHECK(!req_data.offsets.empty()) << "KVServerRowSyncHandle: cmd " << req_meta.cmd
+                                       << " needs the bag offsets of a pooled request (KVWorker::ZPushPooledAll)";
+      CHECK_EQ((req_data.offsets.size() - 1) * w, req_data.vals.size())
+          << "KVServerRowSyncHandle: a pooled Push carries width values per bag";
+    } else if (req_meta.push) {
       CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
       CHECK(req_meta.cmd >= 0 && req_meta.cmd <= kAccumulate) << "KVServerRowSyncHandle: unknown Push cmd " << req_meta.cmd;
     }
@@ -124,7 +142,14 @@ struct KVServerRowSyncHandle {
     h.meta = req_meta;
     h.keys = req_data.keys;
     h.vals = req_data.vals;
-    if (n) {
+    if (pooled) {  // zero keys and nb > 0 bags is a frame like any other: its offsets are checked
+      h.pooled = true;
+      h.nb = req_data.offsets.size() - 1;
+      h.offsets = req_data.offsets;
+      h.doffsets = detail::ToDeviceAsync(req_data.offsets, dev);
+      if (n) h.dkeys = detail::ToDeviceAsync(req_data.keys, dev);
+      if (h.nb) h.dvals = detail::ToDeviceAsync(req_data.vals, dev);
+    } else if (n) {
       h.dkeys = detail::ToDeviceAsync(req_data.keys, dev);
       h.dvals = detail::ToDeviceAsync(req_data.vals, dev);
       if (req_meta.pull) {
@@ -163,10 +188,17 @@ struct KVServerRowSyncHandle {
     const int k = (int)st.held.size();
     const int dev = PostOffice::Get()->device();
     const size_t w = st.width;
-    bool pull = false, ends_iteration = false;
+    bool pull = false, pooled = false, ends_iteration = false;
     for (const Held& h : st.held) {
       pull = pull || (h.meta.pull && h.keys.size());
-      ends_iteration = ends_iteration || (h.meta.cmd == 1 && h.meta.sender == PostOffice::WorkerRankToID(0));
+      pooled = pooled || h.pooled;
+      ends_iteration = ends_iteration || ((h.meta.cmd == 1 || h.meta.cmd == kRowUpdatePooledStep) &&
+                                          h.meta.sender == PostOffice::WorkerRankToID(0));
+    }
+    if (pooled) {
+      RoundPooled(st, k);
+      Answer(st, server, ends_iteration);
+      return;
     }
     std::vector<const uint64_t*> keys(k);
     std::vector<uint64_t> ns(k);
@@ -191,6 +223,35 @@ struct KVServerRowSyncHandle {
                                             device::ThreadStream(), nullptr),
                     "psg_table_update_merged");
     }
+    Answer(st, server, ends_iteration);
+  }
+
+  // A round that holds a pooled frame: the merged update over all k frames, then
+  // the Pull of every held plain PushPull — the updated row for every occurrence.
+  static void RoundPooled(State& st, int k) {
+    std::vector<const uint64_t*> keys(k), offsets(k);
+    std::vector<uint64_t> ns(k), nbs(k);
+    std::vector<const float*> grads(k);
+    for (int j = 0; j < k; ++j) {
+      const Held& h = st.held[j];
+      ns[j] = h.keys.size();
+      nbs[j] = h.nb;
+      keys[j] = ns[j] ? h.dkeys.data() : nullptr;
+      offsets[j] = h.pooled ? h.doffsets.data() : nullptr;
+      grads[j] = h.dvals.empty() ? nullptr : h.dvals.data();
+    }
+    stage::Scope t("server.handle.rows.round");
+    device::Check(psg_table_update_pooled_merged(st.table, k, keys.data(), ns.data(), offsets.data(), nbs.data(),
+                                                 grads.data(), st.lr, st.iteration, device::ThreadStream(), nullptr),
+                  "psg_table_update_pooled_merged");
+    for (const Held& h : st.held)
+      if (!h.dout.empty())
+        device::Check(psg_table_handle_any(st.table, PSG_PULL, h.dkeys.data(), nullptr, h.dout.data(), h.keys.size(),
+                                           device::ThreadStream()),
+                      "psg_table_handle_any");
+  }
+
+  static void Answer(State& st, KVServer<float>* server, bool ends_iteration) {
     if (ends_iteration) ++st.iteration;
     for (const Held& h : st.held) {
       KVPairs<float> res;

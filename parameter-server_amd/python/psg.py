@@ -53,6 +53,7 @@ EXPORTS = [
     "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
+    "psg_table_update_pooled_merged",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
@@ -170,6 +171,7 @@ def lib() -> C.CDLL:
             "psg_table_erase": ([vp, vp, u64, C.POINTER(u64), vp], i32),
             "psg_table_lookup_pooled": ([vp, vp, vp, vp, u64, u64, vp], i32),
             "psg_table_update_pooled": ([vp, vp, vp, vp, u64, u64, f32, i32, vp], i32),
+            "psg_table_update_pooled_merged": ([vp, i32, vp, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -642,6 +644,21 @@ class Table:
         arrival order, and takes one optimizer step."""
         _call("psg_table_update_pooled", self.h, _ptr(keys), _ptr(offsets), _ptr(grads), n, nb, lr, iteration,
               _s(stream))
+
+    def update_pooled_merged(self, frames, ns, nbs, lr: float, iteration: int, stream=None) -> int:
+        """One sync-mode round whose frames may be pooled
+        (psg_table_update_pooled_merged).  frames: a list of (keys, offsets or
+        None, grads) device arrays; frame j has ns[j] keys and, with offsets,
+        nbs[j] bags and one gradient row per bag, without, one gradient row per
+        key (nbs[j] is ignored).  Per id the gradient rows of all its occurrences
+        in all frames are summed from zero in arrival order, then one optimizer
+        step.  Returns MERGED_SAME_LIST or MERGED_SORTED (0: nothing served)."""
+        k = len(frames)
+        arr = lambda col: (C.c_void_p * k)(*[_ptr(f[col]) for f in frames])
+        path = C.c_int(0)
+        _call("psg_table_update_pooled_merged", self.h, k, arr(0), (C.c_uint64 * k)(*ns), arr(1),
+              (C.c_uint64 * k)(*nbs), arr(2), lr, iteration, _s(stream), C.byref(path))
+        return path.value
 
     def close(self) -> None:
         if self.h.value:
