@@ -28,6 +28,8 @@
  *                    ids in bags, one row per bag: the bag's rows summed, and
  *                    that round with the bag's gradient row for each of its ids
  *                    (no pooling in the reference)
+ *   psg_table_lookup_pooled_weighted / _update_pooled_weighted
+ *                    the same with a weight per id, or the bag's mean
  *   psg_table_update_pooled_merged
  *                    the sync-mode round over k frames, pooled or plain
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
@@ -741,6 +743,64 @@ int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* 
 int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets,
                             const float* grads, uint64_t n, uint64_t nb, float lr, int iteration,
                             psg_stream stream);
+/* Weighted and mean bags: the other two poolings of an EmbeddingBag
+ * (per_sample_weights with sum pooling, and mean), on one table.  keys,
+ * offsets, n, nb, out and grads are psg_table_lookup_pooled's and
+ * psg_table_update_pooled's.  weights: n device floats, one per position of
+ * keys, or NULL; always f32, whatever the table's dtype.  mode: PSG_POOL_SUM or
+ * PSG_POOL_MEAN.  The reference has neither.
+ * FORWARD, PSG_POOL_SUM.  For every bag b and column c, acc_t as in
+ * psg_table_lookup_pooled (f32, or f64 for F64 tables):
+ *   acc = +0
+ *   for p in offsets[b] .. offsets[b+1]-1, in that order:
+ *     if keys[p] is present:
+ *       prod = (acc_t)weights[p] * (acc_t)row(keys[p])[c]   -- ONE multiply, rounded to acc_t
+ *       acc  = acc + prod                                    -- ONE add, rounded to acc_t
+ *   out[b*width + c] = (dtype)acc     -- halves: one round-to-nearest-even, at the end
+ * Two roundings per id and never a fused multiply-add: the library is built
+ * with -ffp-contract=off.  An absent id adds nothing whatever its weight (a NaN
+ * weight on an absent id does not reach the bag) and is NOT inserted.  weights
+ * == NULL with PSG_POOL_SUM IS psg_table_lookup_pooled: its path, its kernels,
+ * its bits.
+ * FORWARD, PSG_POOL_MEAN.  weights must be NULL.  acc is the unweighted sum,
+ * then out[b*width + c] = (dtype)(acc / (acc_t)L_b) with L_b = offsets[b+1] -
+ * offsets[b]: the bag's positions, present or not (an absent id is a zero row,
+ * as everywhere in this table).  L_b is converted round-to-nearest and the
+ * divide is ONE correctly rounded division, not a multiply by a reciprocal.  An
+ * empty bag gives a row of +0 and divides nothing.
+ * BACKWARD.  Rows, Adam moments, keys and size end, bit for bit, as after
+ *   psg_table_update_merged(t, PSG_PUSH, 1, {keys}, {n}, {E}, NULL, lr, iteration,
+ *                           stream, NULL)
+ * with, for position i in bag(i) of L_bag(i) positions,
+ *   PSG_POOL_SUM, weights:  E[i*width + c] = weights[i] * grads[bag(i)*width + c]     -- one f32 multiply
+ *   PSG_POOL_MEAN:          E[i*width + c] = grads[bag(i)*width + c] / (float)L_bag(i) -- one f32 division
+ *   PSG_POOL_SUM, NULL:     psg_table_update_pooled itself: its path, its bits
+ * E is never built and no scratch grows with n * width.  The rest is
+ * psg_table_update_pooled's contract: per id the E rows of its occurrences are
+ * summed from +0.0f in arrival order, one f32 add each, the optimizer steps
+ * ONCE, an absent id is inserted once, an empty bag's gradient row is never
+ * read, F32 tables only.  The gradient with respect to the weights is the
+ * caller's.
+ * Refused before any device call, in this order: what the unweighted call
+ * refuses with PSG_ERR_INVALID (a null table; null keys with n > 0; null
+ * offsets or null out / grads with nb > 0; nb == 0 with n > 0); mode outside
+ * {PSG_POOL_SUM, PSG_POOL_MEAN}; PSG_POOL_MEAN with weights; weights not on a
+ * 4-B boundary; for the update iteration < 0 (all PSG_ERR_INVALID).  Then n or
+ * nb above 2^32 - 2 (PSG_ERR_RANGE), then for the update a table that is not
+ * F32 (PSG_ERR_UNSUPPORTED).  nb == 0 is a no-op.  Found on the device as in
+ * the unweighted calls: bad offsets -> PSG_ERR_INVALID, a key out of range ->
+ * PSG_ERR_RANGE, both -> PSG_ERR_INVALID; out is then not written and the
+ * table is bit for bit unchanged.  The lookup keeps its three kernels and its
+ * ONE host synchronisation, at the end (the pooling kernel reads the flags on
+ * the device), and leaves the table as psg_table_lookup_pooled leaves it. */
+#define PSG_POOL_SUM 0
+#define PSG_POOL_MEAN 1
+int psg_table_lookup_pooled_weighted(psg_table* t, const uint64_t* keys, const uint64_t* offsets,
+                                     const float* weights, int mode, void* out, uint64_t n,
+                                     uint64_t nb, psg_stream stream);
+int psg_table_update_pooled_weighted(psg_table* t, const uint64_t* keys, const uint64_t* offsets,
+                                     const float* weights, int mode, const float* grads, uint64_t n,
+                                     uint64_t nb, float lr, int iteration, psg_stream stream);
 /* One sync-mode round whose frames may be pooled: psg_table_update_merged's
  * Push with psg_table_update_pooled's gradient rows.  The five *_host arguments
  * are host arrays of k entries, 1 <= k <= 16; keys_host, offsets_host and

@@ -123,38 +123,55 @@ template <> struct Elem<PSG_BF16> {
 // running sum: f32 for F32 / F16 / BF16, f64 for F64, one lane of A per element
 // of the unit.  add is ONE add per element, in the accumulator's type; round
 // takes the sum back to the stored type (halves: one round-to-nearest-even, at
-// the end).  The sum starts from A{}: +0 in every lane.
+// the end).  The sum starts from A{}: +0 in every lane.  The weighted and the mean
+// bag (psg_table_lookup_pooled_weighted) add two operations, each ONE rounding
+// in the accumulator's element type E and never fused with the add (the library
+// is built with -ffp-contract=off): times, the unit by its id's f32 weight, which
+// sum then takes as add takes a unit; and over, the sum by the bag's length
+// (converted round-to-nearest; a correctly rounded division, no reciprocal).
 template <int DT> struct PoolVec;  // the 16-B unit as elements, and its accumulator
 template <> struct PoolVec<PSG_F32> {
   typedef f32x4 V;
   typedef f32x4 A;
+  typedef float E;
 };
 template <> struct PoolVec<PSG_F64> {
   typedef f64x2 V;
   typedef f64x2 A;
+  typedef double E;
 };
 template <> struct PoolVec<PSG_F16> {
   typedef Elem<PSG_F16>::h8 V;
   typedef Elem<PSG_F16>::f8 A;
+  typedef float E;
 };
 template <> struct PoolVec<PSG_BF16> {
   typedef Elem<PSG_BF16>::b8 V;
   typedef Elem<PSG_BF16>::f8 A;
+  typedef float E;
 };
 template <int DT, bool VEC> struct PoolAcc;
 template <int DT> struct PoolAcc<DT, true> {
   typedef u32x4 U;
   typedef typename PoolVec<DT>::V V;
   typedef typename PoolVec<DT>::A A;
-  __device__ static __forceinline__ A add(A a, U v) {
-    return a + __builtin_convertvector(__builtin_bit_cast(V, v), A);
-  }
+  typedef typename PoolVec<DT>::E E;
+  __device__ static __forceinline__ A widen(U v) { return __builtin_convertvector(__builtin_bit_cast(V, v), A); }
+  __device__ static __forceinline__ A sum(A a, A x) { return a + x; }
+  __device__ static __forceinline__ A add(A a, U v) { return sum(a, widen(v)); }
+  __device__ static __forceinline__ A times(float w, U v) { return (E)w * widen(v); }
+  __device__ static __forceinline__ A over(A a, uint32_t len) { return a / (E)len; }
   __device__ static __forceinline__ U round(A a) { return __builtin_bit_cast(U, __builtin_convertvector(a, V)); }
 };
 template <int DT> struct PoolAcc<DT, false> {
   typedef typename Elem<DT>::T U;
   typedef typename std::conditional<DT == PSG_F64, double, float>::type A;
-  __device__ static __forceinline__ A add(A a, U v) { return a + (A)v; }
+  typedef A E;
+  __device__ static __forceinline__ A widen(U v) { return (A)v; }
+  __device__ static __forceinline__ A sum(A a, A x) { return a + x; }
+  __device__ static __forceinline__ A add(A a, U v) { return sum(a, widen(v)); }
+  __device__ static __forceinline__ A times(float w, U v) { return (E)w * widen(v); }
+  __device__ static __forceinline__ A over(A a, uint32_t len) { return a / (E)len; }
   __device__ static __forceinline__ U round(A a) { return (U)a; }
 };
 #endif

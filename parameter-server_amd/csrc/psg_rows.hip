@@ -679,11 +679,19 @@ __global__ __launch_bounds__(256) void k_offsets_check(const uint64_t* __restric
 // atomics, no LDS.  The loop is a chain slots -> row unit -> add; the slot two
 // ahead and the row unit one ahead are loaded before the current add.  An
 // absent slot (kAbsent) loads nothing and adds nothing.
-template <typename U, typename ACC>
+// POOL (psg_table_lookup_pooled_weighted): kPoolWeighted reads weights[p] beside
+// slots[p], two ahead as the slot is, and adds ACC::times(weight, unit) — one
+// multiply, then sum's one add; the chain is slots, weights -> row unit -> mul ->
+// add.  An absent slot's weight is loaded and not used.  kPoolMean divides the
+// sum of a bag that holds a position by its length (ACC::over) before the one
+// store.  kPoolSum reads no weight and is the code it was.
+enum { kPoolSum = 0, kPoolWeighted = 1, kPoolMean = 2 };
+template <typename U, typename ACC, int POOL = kPoolSum>
 __global__ __launch_bounds__(256) void k_rows_pool(const U* __restrict__ R, const uint32_t* __restrict__ slots,
                                                    const uint64_t* __restrict__ offsets, U* __restrict__ out,
                                                    uint64_t nb, uint32_t upr, uint32_t rpt,
-                                                   const int* __restrict__ gate) {
+                                                   const int* __restrict__ gate,
+                                                   const float* __restrict__ weights = nullptr) {
   if (gate[R_RANGE] | gate[R_OFFSETS]) return;
   const uint64_t ntiles = (nb + rpt - 1) / rpt;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -696,19 +704,34 @@ __global__ __launch_bounds__(256) void k_rows_pool(const U* __restrict__ R, cons
       const uint32_t c = w.c;
       uint32_t p = (uint32_t)offsets[b];  // <= n <= 2^32 - 2: checked
       const uint32_t pe = (uint32_t)offsets[b + 1];
+      [[maybe_unused]] const uint32_t len = pe - p;
       typename ACC::A acc = {};  // +0
       if (p < pe) {
         uint32_t s0 = slots[p];
         uint32_t s1 = p + 1 < pe ? slots[p + 1] : kAbsent;
+        [[maybe_unused]] float w0 = 0, w1 = 0;
+        if constexpr (POOL == kPoolWeighted) {
+          w0 = weights[p];
+          if (p + 1 < pe) w1 = weights[p + 1];
+        }
         U v = {};
         if (s0 != kAbsent) v = R[(uint64_t)s0 * upr + c];
         for (; p < pe; ++p) {
           const uint32_t s2 = p + 2 < pe ? slots[p + 2] : kAbsent;
+          [[maybe_unused]] float w2 = 0;
+          if constexpr (POOL == kPoolWeighted)
+            if (p + 2 < pe) w2 = weights[p + 2];
           U vn = {};
           if (s1 != kAbsent) vn = R[(uint64_t)s1 * upr + c];
-          if (s0 != kAbsent) acc = ACC::add(acc, v);
+          if constexpr (POOL == kPoolWeighted) {
+            if (s0 != kAbsent) acc = ACC::sum(acc, ACC::times(w0, v));
+            w0 = w1, w1 = w2;
+          } else {
+            if (s0 != kAbsent) acc = ACC::add(acc, v);
+          }
           s0 = s1, s1 = s2, v = vn;
         }
+        if constexpr (POOL == kPoolMean) acc = ACC::over(acc, len);
       }
       out[b * upr + c] = ACC::round(acc);
     }
@@ -1063,13 +1086,31 @@ __global__ __launch_bounds__(256) void k_row_index(uint32_t* __restrict__ idx, u
 // (psg_table_update_pooled_merged): f.off[j] is the first row of frame j,
 // f.vals[j] its array moved back by that many rows, so `row` indexes it as it is;
 // a block keeps the addresses in LDS, as k_rows_walk_merge does.
+// kPool: what an occurrence receives of its gradient row
+// (psg_table_update_pooled_weighted).  WeightedArray: the row times w[p], w
+// indexed as `bags` is (the walk's positions); MeanArray: the row divided by its
+// bag's length, read from the checked offsets.  One f32 operation per element.
 template <typename U> struct OneArray {
   static constexpr bool kFrames = false;
+  static constexpr int kPool = kPoolSum;
   const U* grads;
 };
 struct FrameArrays {
   static constexpr bool kFrames = true;
+  static constexpr int kPool = kPoolSum;
   Frames f;
+};
+template <typename U> struct WeightedArray {
+  static constexpr bool kFrames = false;
+  static constexpr int kPool = kPoolWeighted;
+  const U* grads;
+  const float* w;
+};
+template <typename U> struct MeanArray {
+  static constexpr bool kFrames = false;
+  static constexpr int kPool = kPoolMean;
+  const U* grads;
+  const uint64_t* offsets;
 };
 
 // Pass 2 of the pooled updates: k_rows_walk_merge's walk with a gradient-row
@@ -1085,7 +1126,11 @@ struct FrameArrays {
 // FrameArrays (frame_of over the frames' first rows: 15 compares and one 8-B
 // LDS read an occurrence).  STRICT (OneArray only): the list ascends strictly,
 // nothing was sorted; row u's one occurrence is position u, bags is bag_of
-// itself and seg is not read.
+// itself and seg is not read.  SRC::kPool: a weighted occurrence's weight is
+// loaded beside its row index, two ahead, and a mean occurrence's bag length
+// beside its gradient unit, one ahead (two words of `offsets` the row's lanes
+// share), so the chain stays (bags[p], w[p]) -> gradient unit -> mul -> add; the
+// multiply or the division is one f32 operation and the add is the one there was.
 template <typename UNIT, typename SRC, bool STRICT>
 __global__ __launch_bounds__(256) void k_rows_walk_pool(typename UNIT::U* __restrict__ R, double* __restrict__ M,
                                                         const uint32_t* __restrict__ slots,
@@ -1119,18 +1164,45 @@ __global__ __launch_bounds__(256) void k_rows_walk_pool(typename UNIT::U* __rest
         else
           return UNIT::load_grad(src.grads, (uint64_t)row * upr + c);
       };
+      // MeanArray: the length of gradient row `row`'s bag, as the division takes it
+      [[maybe_unused]] auto len_of = [&](uint32_t row) {
+        if constexpr (SRC::kPool == kPoolMean)
+          return (float)(uint32_t)(src.offsets[(uint64_t)row + 1] - src.offsets[row]);
+        else
+          return 0.0f;
+      };
       UNIT x;
       x.locate(slots[u], c, upr, prm);
       x.load_state(R, M, prm);  // issued here, used after the sum
       uint32_t b1 = p0 + 1 < pe ? bags[p0 + 1] : 0;
-      U v = grad_at(bags[p0]);
+      [[maybe_unused]] float f = 0, f1 = 0;  // the factors of v and of the occurrence behind it
+      if constexpr (SRC::kPool == kPoolWeighted) {
+        f = src.w[p0];
+        if (p0 + 1 < pe) f1 = src.w[p0 + 1];
+      }
+      const uint32_t bfirst = bags[p0];
+      U v = grad_at(bfirst);
+      if constexpr (SRC::kPool == kPoolMean) f = len_of(bfirst);
       U s = {};  // +0.0f
       for (uint32_t p = p0; p < pe; ++p) {
         const uint32_t b2 = p + 2 < pe ? bags[p + 2] : 0;
+        [[maybe_unused]] float f2 = 0;
+        if constexpr (SRC::kPool == kPoolWeighted)
+          if (p + 2 < pe) f2 = src.w[p + 2];
         U vn = v;
-        if (p + 1 < pe) vn = grad_at(b1);
-        s = s + v;
+        if (p + 1 < pe) {
+          vn = grad_at(b1);
+          if constexpr (SRC::kPool == kPoolMean) f1 = len_of(b1);
+        }
+        if constexpr (SRC::kPool == kPoolWeighted)
+          s = s + f * v;
+        else if constexpr (SRC::kPool == kPoolMean)
+          s = s + v / f;
+        else
+          s = s + v;
         b1 = b2, v = vn;
+        if constexpr (SRC::kPool == kPoolWeighted) f = f1, f1 = f2;
+        if constexpr (SRC::kPool == kPoolMean) f = f1;
       }
       x.step(s, prm);
       x.store_state(R, M, prm);
@@ -1840,29 +1912,50 @@ int launch_offsets_check(const uint64_t* offsets, uint64_t n, uint64_t nb, int* 
   return PSG_OK;
 }
 
+// What the weighted calls refuse behind pooled_args; the unweighted calls come
+// through with no weights and PSG_POOL_SUM.
+int pool_mode_args(const char* name, const float* weights, int mode) {
+  PSG_REQUIRE(mode == PSG_POOL_SUM || mode == PSG_POOL_MEAN, PSG_ERR_INVALID, "%s: mode %d is no pooling mode", name,
+              mode);
+  PSG_REQUIRE(mode != PSG_POOL_MEAN || !weights, PSG_ERR_INVALID, "%s: weights with PSG_POOL_MEAN", name);
+  PSG_REQUIRE((reinterpret_cast<uintptr_t>(weights) & 3u) == 0, PSG_ERR_INVALID, "%s: weights not on a 4-B boundary",
+              name);
+  return PSG_OK;
+}
+
+// pool: kPoolSum is the unweighted call's kernel, launched as it was
 template <int DT, bool VEC>
-int launch_pool(psg_table* t, const uint64_t* offsets, void* out, uint64_t nb, uint32_t upr, hipStream_t st) {
+int launch_pool(psg_table* t, const uint64_t* offsets, const float* weights, int pool, void* out, uint64_t nb,
+                uint32_t upr, hipStream_t st) {
   using ACC = PoolAcc<DT, VEC>;
   using U = typename ACC::U;
   const uint32_t rpt = rows_per_tile(upr);
-  k_rows_pool<U, ACC><<<grid_for((nb + rpt - 1) / rpt), kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out,
-                                                                         nb, upr, rpt, t->gate);
+  const unsigned g = grid_for((nb + rpt - 1) / rpt);
+  if (pool == kPoolWeighted)
+    k_rows_pool<U, ACC, kPoolWeighted><<<g, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr, rpt,
+                                                             t->gate, weights);
+  else if (pool == kPoolMean)
+    k_rows_pool<U, ACC, kPoolMean><<<g, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr, rpt,
+                                                         t->gate);
+  else
+    k_rows_pool<U, ACC><<<g, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr, rpt, t->gate);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
 
 template <int DT>
-int pool_dtype(psg_table* t, const uint64_t* offsets, void* out, uint64_t nb, hipStream_t st) {
-  // 16-B units under accumulate_vec's condition for a Pull
+int pool_dtype(psg_table* t, const uint64_t* offsets, const float* weights, int pool, void* out, uint64_t nb,
+               hipStream_t st) {
+  // 16-B units under accumulate_vec's condition for a Pull (the weights are read as words either way)
   if (accumulate_vec(t, PSG_PULL, nullptr, out))
-    return launch_pool<DT, true>(t, offsets, out, nb, t->width / Elem<DT>::kVec, st);
-  return launch_pool<DT, false>(t, offsets, out, nb, t->width, st);
+    return launch_pool<DT, true>(t, offsets, weights, pool, out, nb, t->width / Elem<DT>::kVec, st);
+  return launch_pool<DT, false>(t, offsets, weights, pool, out, nb, t->width, st);
 }
 
-int lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, void* out, uint64_t n, uint64_t nb,
-                  psg_stream stream) {
-  const char* name = "psg_table_lookup_pooled";
+int lookup_pooled(const char* name, psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* weights,
+                  int mode, void* out, uint64_t n, uint64_t nb, psg_stream stream) {
   PSG_TRY(pooled_args(name, t, keys, offsets, out, "out", n, nb));
+  PSG_TRY(pool_mode_args(name, weights, mode));
   PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
   PSG_REQUIRE(nb <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 bags in one request", name);
   if (nb == 0) return PSG_OK;
@@ -1876,13 +1969,14 @@ int lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, v
         keys, n, t->keys, t->size, t->key_begin, t->key_end, t->slots, t->gate);
     PSG_HIP(hipGetLastError());
   }
+  const int pool = mode == PSG_POOL_MEAN ? kPoolMean : weights ? kPoolWeighted : kPoolSum;
   switch (t->dtype) {
-    case PSG_F32: PSG_TRY(pool_dtype<PSG_F32>(t, offsets, out, nb, st)); break;
-    case PSG_F64: PSG_TRY(pool_dtype<PSG_F64>(t, offsets, out, nb, st)); break;
-    case PSG_F16: PSG_TRY(pool_dtype<PSG_F16>(t, offsets, out, nb, st)); break;
-    default: PSG_TRY(pool_dtype<PSG_BF16>(t, offsets, out, nb, st)); break;
+    case PSG_F32: PSG_TRY(pool_dtype<PSG_F32>(t, offsets, weights, pool, out, nb, st)); break;
+    case PSG_F64: PSG_TRY(pool_dtype<PSG_F64>(t, offsets, weights, pool, out, nb, st)); break;
+    case PSG_F16: PSG_TRY(pool_dtype<PSG_F16>(t, offsets, weights, pool, out, nb, st)); break;
+    default: PSG_TRY(pool_dtype<PSG_BF16>(t, offsets, weights, pool, out, nb, st)); break;
   }
-  // the one synchronisation: keys and offsets no longer read, the reply in memory, the flags on the host
+  // the one synchronisation: keys, offsets and weights no longer read, the reply in memory, the flags on the host
   PSG_HIP(hipMemcpyAsync(t->flags_host, t->gate, kNFlags * sizeof(int), hipMemcpyDeviceToHost, st));
   PSG_HIP(hipStreamSynchronize(st));
   PSG_TRY(require_offsets(t, name, n));
@@ -1892,10 +1986,43 @@ int lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, v
 // The pooled walk for one unit type: over the plan's unique rows, their gradient
 // rows in the one array `grads` or (f not null, always with a plan) in the
 // round's frames; without a plan the strict walk over the list's n rows.
+// The weighted or the mean walk (src: WeightedArray / MeanArray) over the plan's
+// unique rows with bags[p] the gradient row of sorted position p, or without a
+// plan the strict walk with bags = bag_of.
+template <typename UNIT, typename SRC>
+int launch_walk_scaled(psg_table* t, const AnyPlan* p, const uint32_t* bags, const SRC& src, uint64_t n, uint32_t upr,
+                       const typename UNIT::Params& prm, hipStream_t st) {
+  using U = typename UNIT::U;
+  const uint32_t rpt = rows_per_tile(upr);
+  const uint64_t rows = p ? p->m : n;
+  const unsigned g = grid_for((rows + rpt - 1) / rpt);
+  if (p)
+    k_rows_walk_pool<UNIT, SRC, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, bags, src, rows, upr,
+                                                             rpt, prm);
+  else
+    k_rows_walk_pool<UNIT, SRC, true><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, nullptr, bags, src, rows, upr,
+                                                            rpt, prm);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+// What the pooled update's occurrences receive of their gradient rows: the row
+// (no weights, no offsets), the row times weights[.] at the walk's positions, or
+// the row over its bag's length.
+struct PoolScale {
+  const float* weights;
+  const uint64_t* offsets;
+};
+
 template <typename UNIT>
 int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, const float* grads, const Frames* f,
-                     uint64_t n, uint32_t upr, const typename UNIT::Params& prm, hipStream_t st) {
+                     const PoolScale& sc, uint64_t n, uint32_t upr, const typename UNIT::Params& prm, hipStream_t st) {
   using U = typename UNIT::U;
+  if (sc.weights)
+    return launch_walk_scaled<UNIT>(t, p, bag_of, WeightedArray<U>{(const U*)grads, sc.weights}, n, upr, prm, st);
+  if (sc.offsets)
+    return launch_walk_scaled<UNIT>(t, p, p ? p->perm : bag_of, MeanArray<U>{(const U*)grads, sc.offsets}, n, upr, prm,
+                                    st);
   const uint32_t rpt = rows_per_tile(upr);
   const uint64_t rows = p ? p->m : n;
   const unsigned g = grid_for((rows + rpt - 1) / rpt);
@@ -1916,18 +2043,38 @@ int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, con
 // vec: 16-B units (optimize_vec's condition for a Push, on every gradient array)
 template <bool ADAM>
 int pooled_adam(psg_table* t, bool vec, const AnyPlan* p, const uint32_t* bag_of, const float* grads, const Frames* f,
-                uint64_t n, float lr, int iteration, hipStream_t st) {
+                const PoolScale& sc, uint64_t n, float lr, int iteration, hipStream_t st) {
   if (vec)
-    return launch_walk_pool<OptUnit<ADAM, true>>(t, p, bag_of, grads, f, n, t->width / 4,
+    return launch_walk_pool<OptUnit<ADAM, true>>(t, p, bag_of, grads, f, sc, n, t->width / 4,
                                                  {t->width, lr, adam_args(t, iteration)}, st);
-  return launch_walk_pool<OptUnit<ADAM, false>>(t, p, bag_of, grads, f, n, t->width,
+  return launch_walk_pool<OptUnit<ADAM, false>>(t, p, bag_of, grads, f, sc, n, t->width,
                                                 {t->width, lr, adam_args(t, iteration)}, st);
 }
 
-// path (may be null): how the list was served, as psg_table_update_merged reports it
-int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads,
-                  uint64_t n, uint64_t nb, float lr, int iteration, psg_stream stream, int* path) {
+// bags[p] = bag_of[perm[p]] and w[p] = weights[perm[p]] for p < n: the weighted
+// update's two per-occurrence words in sorted order, gathered once behind the
+// sort so that the walk reads both at its own position, as it reads the sort's
+// payload, and not through perm (one more dependent load an occurrence).
+// 4 B read in order and 8 B gathered per id, 8 B written in order.
+__global__ __launch_bounds__(256) void k_pool_gather(const uint32_t* __restrict__ perm,
+                                                     const uint32_t* __restrict__ bag_of,
+                                                     const float* __restrict__ weights, uint32_t* __restrict__ bags,
+                                                     float* __restrict__ w, uint64_t n) {
+  for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t i = perm[p];  // a position of the list: the sort permutes 0 .. n - 1
+    bags[p] = bag_of[i];
+    w[p] = weights[i];
+  }
+}
+
+// path (may be null): how the list was served, as psg_table_update_merged reports it.
+// weights, mode: psg_table_update_pooled_weighted's; the unweighted callers pass
+// none and PSG_POOL_SUM.
+int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* weights,
+                  int mode, const float* grads, uint64_t n, uint64_t nb, float lr, int iteration, psg_stream stream,
+                  int* path) {
   PSG_TRY(pooled_args(name, t, keys, offsets, grads, "grads", n, nb));
+  PSG_TRY(pool_mode_args(name, weights, mode));
   PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
   PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
   PSG_REQUIRE(nb <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 bags in one request", name);
@@ -1953,21 +2100,43 @@ int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
   const bool strict = !t->flags_host[R_UNSORTED];  // as PSG_MERGED_SAME_LIST is decided for k = 1
   AnyScratch a;
   PSG_TRY(any_scratch(t, n, &a));
-  k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, 0, a.p0);
-  PSG_HIP(hipGetLastError());
+  // a weighted list out of order: the sort carries positions, and bag_of is
+  // written behind it, where the sort's other position buffer is free
+  const bool by_position = weights && !strict;
+  const uint32_t* bags = a.p0;  // what the walk reads at its positions (sorted path, unweighted: plan.perm)
+  PoolScale sc = {weights, mode == PSG_POOL_MEAN ? offsets : nullptr};
+  if (!by_position) {
+    k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, 0, a.p0);
+    PSG_HIP(hipGetLastError());
+  }
   AnyPlan plan;
   const AnyPlan* p = nullptr;
   if (strict) {
     PSG_TRY(resolve_finish(t, keys, n, st));
   } else {
     PSG_HIP(hipMemcpyAsync(a.k0, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    PSG_TRY(plan_scratch(t, a, n, &plan, st, true));
+    PSG_TRY(plan_scratch(t, a, n, &plan, st, !by_position));
     p = &plan;
   }
+  if (by_position) {
+    // behind plan_scratch on the stream both key buffers are spent (the sorted
+    // keys are cut into runs, the unique list is resolved): a.k0's 8 n bytes
+    // take the two gathered arrays, n words each
+    uint32_t* bag_of = plan.perm == a.p0 ? a.p1 : a.p0;
+    uint32_t* sorted_bags = (uint32_t*)a.k0;
+    float* sorted_w = (float*)(sorted_bags + n);
+    k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, 0, bag_of);
+    PSG_HIP(hipGetLastError());
+    k_pool_gather<<<grid_for((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(plan.perm, bag_of, weights, sorted_bags,
+                                                                          sorted_w, n);
+    PSG_HIP(hipGetLastError());
+    bags = sorted_bags;
+    sc.weights = sorted_w;
+  }
   const bool vec = optimize_vec(t, PSG_PUSH, grads, nullptr);
-  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, p, a.p0, grads, nullptr, n, lr, iteration, st)
-                  : pooled_adam<false>(t, vec, p, a.p0, grads, nullptr, n, lr, iteration, st));
-  // complete on return: keys, offsets and grads no longer read
+  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, p, bags, grads, nullptr, sc, n, lr, iteration, st)
+                  : pooled_adam<false>(t, vec, p, bags, grads, nullptr, sc, n, lr, iteration, st));
+  // complete on return: keys, offsets, weights and grads no longer read
   PSG_HIP(hipStreamSynchronize(st));
   if (path) *path = strict ? PSG_MERGED_SAME_LIST : PSG_MERGED_SORTED;
   return PSG_OK;
@@ -2019,7 +2188,8 @@ int update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys, const
   PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
   if (path_host) *path_host = 0;
   if (!pooled) return update_merged(t, PSG_PUSH, k, keys, ns, grads, nullptr, lr, iteration, stream, path_host);
-  if (k == 1) return update_pooled(name, t, keys[0], offsets[0], grads[0], ns[0], nbs[0], lr, iteration, stream, path_host);
+  if (k == 1) return update_pooled(name, t, keys[0], offsets[0], nullptr, PSG_POOL_SUM, grads[0], ns[0], nbs[0], lr, iteration, stream,
+                         path_host);
   if (N == 0 && G == 0) return PSG_OK;  // no key and no bag: nothing to check either
   hipStream_t st = (hipStream_t)stream;
   // the front half: every offsets array checked before anything else reads it,
@@ -2060,8 +2230,8 @@ int update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys, const
   }
   AnyPlan plan;
   PSG_TRY(plan_scratch(t, a, N, &plan, st, true));
-  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, &plan, nullptr, nullptr, &f, N, lr, iteration, st)
-                  : pooled_adam<false>(t, vec, &plan, nullptr, nullptr, &f, N, lr, iteration, st));
+  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, &plan, nullptr, nullptr, &f, {}, N, lr, iteration, st)
+                  : pooled_adam<false>(t, vec, &plan, nullptr, nullptr, &f, {}, N, lr, iteration, st));
   // complete on return: keys, offsets and grads no longer read
   PSG_HIP(hipStreamSynchronize(st));
   if (path_host) *path_host = PSG_MERGED_SORTED;
@@ -2234,12 +2404,25 @@ int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* er
 
 int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, void* out, uint64_t n,
                             uint64_t nb, psg_stream stream) {
-  return lookup_pooled(t, keys, offsets, out, n, nb, stream);
+  return lookup_pooled("psg_table_lookup_pooled", t, keys, offsets, nullptr, PSG_POOL_SUM, out, n, nb, stream);
+}
+
+int psg_table_lookup_pooled_weighted(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* weights,
+                                     int mode, void* out, uint64_t n, uint64_t nb, psg_stream stream) {
+  return lookup_pooled("psg_table_lookup_pooled_weighted", t, keys, offsets, weights, mode, out, n, nb, stream);
 }
 
 int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads,
                             uint64_t n, uint64_t nb, float lr, int iteration, psg_stream stream) {
-  return update_pooled("psg_table_update_pooled", t, keys, offsets, grads, n, nb, lr, iteration, stream, nullptr);
+  return update_pooled("psg_table_update_pooled", t, keys, offsets, nullptr, PSG_POOL_SUM, grads, n, nb, lr, iteration,
+                       stream, nullptr);
+}
+
+int psg_table_update_pooled_weighted(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* weights,
+                                     int mode, const float* grads, uint64_t n, uint64_t nb, float lr, int iteration,
+                                     psg_stream stream) {
+  return update_pooled("psg_table_update_pooled_weighted", t, keys, offsets, weights, mode, grads, n, nb, lr, iteration,
+                       stream, nullptr);
 }
 
 int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys_host, const uint64_t* ns_host,

@@ -28,6 +28,7 @@ DENSE, SORTED = 0, 1
 PUSH, PULL = 1, 2
 RUN_ONE_BY_ONE, RUN_SAME_LIST, RUN_STRIDED = 0, 1, 2
 MERGED_SAME_LIST, MERGED_SORTED = 1, 2
+POOL_SUM, POOL_MEAN = 0, 1
 H2D, D2H, D2D = 0, 1, 2
 
 _NP = {F32: np.float32, F64: np.float64, F16: np.float16, BF16: np.uint16}
@@ -53,7 +54,7 @@ EXPORTS = [
     "psg_table_handle_any", "psg_table_update_any", "psg_table_update_merged",
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
-    "psg_table_update_pooled_merged",
+    "psg_table_lookup_pooled_weighted", "psg_table_update_pooled_weighted", "psg_table_update_pooled_merged",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
@@ -171,6 +172,8 @@ def lib() -> C.CDLL:
             "psg_table_erase": ([vp, vp, u64, C.POINTER(u64), vp], i32),
             "psg_table_lookup_pooled": ([vp, vp, vp, vp, u64, u64, vp], i32),
             "psg_table_update_pooled": ([vp, vp, vp, vp, u64, u64, f32, i32, vp], i32),
+            "psg_table_lookup_pooled_weighted": ([vp, vp, vp, vp, i32, vp, u64, u64, vp], i32),
+            "psg_table_update_pooled_weighted": ([vp, vp, vp, vp, i32, vp, u64, u64, f32, i32, vp], i32),
             "psg_table_update_pooled_merged": ([vp, i32, vp, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
@@ -644,6 +647,22 @@ class Table:
         arrival order, and takes one optimizer step."""
         _call("psg_table_update_pooled", self.h, _ptr(keys), _ptr(offsets), _ptr(grads), n, nb, lr, iteration,
               _s(stream))
+
+    def lookup_pooled_weighted(self, keys, offsets, weights, mode: int, out, n: int, nb: int, stream=None) -> None:
+        """The pooled lookup with a weight per id or as a mean
+        (psg_table_lookup_pooled_weighted).  weights: n device float32, one per
+        position of keys, or None; mode: POOL_SUM (out[b] = sum of weight * row) or
+        POOL_MEAN (the unweighted sum over the bag's length; weights must be None)."""
+        _call("psg_table_lookup_pooled_weighted", self.h, _ptr(keys), _ptr(offsets), _ptr(weights), mode, _ptr(out), n,
+              nb, _s(stream))
+
+    def update_pooled_weighted(self, keys, offsets, weights, mode: int, grads, n: int, nb: int, lr: float,
+                               iteration: int, stream=None) -> None:
+        """Its backward (psg_table_update_pooled_weighted): every occurrence of an id
+        receives its bag's gradient row times its weight (POOL_SUM) or over the
+        bag's length (POOL_MEAN, weights None); then as update_pooled."""
+        _call("psg_table_update_pooled_weighted", self.h, _ptr(keys), _ptr(offsets), _ptr(weights), mode, _ptr(grads),
+              n, nb, lr, iteration, _s(stream))
 
     def update_pooled_merged(self, frames, ns, nbs, lr: float, iteration: int, stream=None) -> int:
         """One sync-mode round whose frames may be pooled
