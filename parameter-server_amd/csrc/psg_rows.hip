@@ -1216,20 +1216,108 @@ unsigned grid_for(uint64_t blocks) {
   return blocks ? (unsigned)blocks : 1u;
 }
 
-template <typename U>
-int launch_move(const void* src, void* dst, const uint32_t* to, uint64_t nrows, uint32_t upr, hipStream_t st) {
+unsigned grid_per_lane(uint64_t n) { return grid_for((n + kBlock - 1) / kBlock); }  // one lane per element
+
+// The geometry of every walk over rows of upr units: the rows of a tile, a block per tile.
+struct Tiles {
+  uint32_t rpt;
+  unsigned grid;
+};
+Tiles tiles_for(uint64_t rows, uint32_t upr) {
   const uint32_t rpt = rows_per_tile(upr);
-  k_rows_move<U><<<grid_for((nrows + rpt - 1) / rpt), kBlock, 0, st>>>((const U*)src, (U*)dst, to, nrows, upr, rpt);
+  return {rpt, grid_for((rows + rpt - 1) / rpt)};
+}
+
+// ---- what several calls refuse, under the call's name ----------------------------
+int require_table(const char* name, const psg_table* t) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  return PSG_OK;
+}
+int require_keys(const char* name, const uint64_t* keys) {
+  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
+  return PSG_OK;
+}
+int require_count(const char* name, uint64_t n, const char* what = "keys") {
+  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 %s in one request", name, what);
+  return PSG_OK;
+}
+// a round's keys (or gradient rows) so far and one more frame's
+int require_round_count(const char* name, uint64_t N, uint64_t n, const char* what = "keys") {
+  PSG_REQUIRE(n <= kMaxRows && N + n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 %s in one round", name, what);
+  return PSG_OK;
+}
+int require_frame_count(const char* name, int k) {
+  PSG_REQUIRE(k >= 1 && k <= kMaxFrames, PSG_ERR_INVALID, "%s: %d frames outside [1, %d]", name, k, kMaxFrames);
+  return PSG_OK;
+}
+int require_update_flags(const char* name, int flags) {
+  PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
+              "%s: flags %d are neither PUSH nor PUSH|PULL", name, flags);
+  return PSG_OK;
+}
+int require_iteration(const char* name, int iteration) {
+  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
+  return PSG_OK;
+}
+int require_f32(const char* name, const psg_table* t) {
+  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
+  return PSG_OK;
+}
+
+// ---- rows as raw bytes ------------------------------------------------------------
+// f(U{}) with U the unsigned unit of unit_bytes bytes: 16, 8, 4, else 2.
+template <typename F>
+int for_raw_unit(uint32_t unit_bytes, F&& f) {
+  switch (unit_bytes) {
+    case 16: return f(u32x4{});
+    case 8: return f(uint64_t{});
+    case 4: return f(uint32_t{});
+    default: return f(uint16_t{});
+  }
+}
+
+// The table's own rows (insert, erase): 16, 4 or 2 B, whichever the row length allows; never 8.
+uint32_t table_unit_bytes(const psg_table* t) {
+  const uint32_t rb = t->width * (uint32_t)t->esize;
+  return rb % 16 == 0 ? 16 : rb % 4 == 0 ? 4 : 2;
+}
+
+// 16-B vectors when every row, here and in the request, starts on 16 B
+bool accumulate_vec(const psg_table* t, int op, const void* vals, const void* out) {
+  return ((uint64_t)t->width * t->esize) % 16 == 0 && (!(op & PSG_PUSH) || aligned16(vals)) &&
+         (!(op & PSG_PULL) || aligned16(out));
+}
+
+// A request's rows (assign, lookup): 16 B under accumulate_vec's condition, else the element.
+uint32_t request_unit_bytes(const psg_table* t, int op, const void* vals, const void* out) {
+  return accumulate_vec(t, op, vals, out) ? 16 : (uint32_t)t->esize;
+}
+
+// dst row map[j] = src row j (k_rows_move; src null: a zero row) or, take, dst
+// row j = src row map[j] (k_rows_take), for j < nrows.
+template <typename U>
+int launch_move(bool take, const void* src, void* dst, const uint32_t* map, uint64_t nrows, uint32_t upr,
+                hipStream_t st) {
+  const Tiles g = tiles_for(nrows, upr);
+  if (take)
+    k_rows_take<U><<<g.grid, kBlock, 0, st>>>((const U*)src, (U*)dst, map, nrows, upr, g.rpt);
+  else
+    k_rows_move<U><<<g.grid, kBlock, 0, st>>>((const U*)src, (U*)dst, map, nrows, upr, g.rpt);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
 
-// rows move as raw bytes: 16-B, 4-B or 2-B units, whichever the row length allows
-int move_rows(const psg_table* t, const void* src, void* dst, const uint32_t* to, uint64_t nrows, hipStream_t st) {
+// value rows move as raw bytes (a moment row is width 16-B units: launch_move<u32x4>)
+int move_rows(const psg_table* t, bool take, const void* src, void* dst, const uint32_t* map, uint64_t nrows,
+              hipStream_t st) {
   const uint32_t rb = t->width * (uint32_t)t->esize;
-  if (rb % 16 == 0) return launch_move<u32x4>(src, dst, to, nrows, rb / 16, st);
-  if (rb % 4 == 0) return launch_move<uint32_t>(src, dst, to, nrows, rb / 4, st);
-  return launch_move<uint16_t>(src, dst, to, nrows, rb / 2, st);
+  return for_raw_unit(table_unit_bytes(t), [&](auto u) -> int {
+    using U = decltype(u);
+    if constexpr (sizeof(U) == 8)
+      __builtin_unreachable();  // table_unit_bytes never says 8, and no 8-B move is built
+    else
+      return launch_move<U>(take, src, dst, map, nrows, rb / (uint32_t)sizeof(U), st);
+  });
 }
 
 inline uint64_t mom_row_bytes(const psg_table* t) { return (uint64_t)t->width * 2 * sizeof(double); }
@@ -1245,14 +1333,71 @@ int ensure_slots(psg_table* t, uint64_t n) {
   return PSG_OK;
 }
 
-// Launch the resolve of q into t->slots and wait for its flags.
-int resolve(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) {
-  memset(t->flags_host, 0, kNFlags * sizeof(int));
-  const uint64_t ntiles = (n + kRowTile - 1) / kRowTile;
-  k_rows_resolve<<<grid_for(ntiles), kBlock, 0, st>>>(q, n, t->keys, t->size, t->key_begin, t->key_end, t->slots,
-                                                      t->flags);
+// ---- the front half of a request ----------------------------------------------------
+// Pass 1: q's slots into t->slots and its flags into `flags`.  ordered: k_rows_resolve,
+// which looks at order and absence as well; else k_rows_resolve_any, for a list in any order.
+int launch_resolve(psg_table* t, const uint64_t* q, uint64_t n, int* flags, bool ordered, hipStream_t st) {
+  const unsigned g = grid_for((n + kRowTile - 1) / kRowTile);
+  if (ordered)
+    k_rows_resolve<<<g, kBlock, 0, st>>>(q, n, t->keys, t->size, t->key_begin, t->key_end, t->slots, flags);
+  else
+    k_rows_resolve_any<<<g, kBlock, 0, st>>>(q, n, t->keys, t->size, t->key_begin, t->key_end, t->slots, flags);
   PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+int launch_offsets_check(const uint64_t* offsets, uint64_t n, uint64_t nb, int* flags, hipStream_t st) {
+  k_offsets_check<<<grid_per_lane(nb + 1), kBlock, 0, st>>>(offsets, nb, n, flags);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+// The flags on the host: t->flags_host cleared, `checks` (the pooled calls' offsets
+// checks, which raise flags of their own in front of the resolve), the resolve of q where
+// there are keys, one synchronisation.  Nothing is written to the table.
+template <typename F>
+int resolve_first(psg_table* t, const uint64_t* q, uint64_t n, bool ordered, hipStream_t st, F&& checks) {
+  PSG_TRY(ensure_slots(t, n));
+  memset(t->flags_host, 0, kNFlags * sizeof(int));
+  PSG_TRY(checks());
+  if (n) PSG_TRY(launch_resolve(t, q, n, t->flags, ordered, st));
   PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+int resolve_first(psg_table* t, const uint64_t* q, uint64_t n, bool ordered, hipStream_t st) {
+  return resolve_first(t, q, n, ordered, st, [] { return (int)PSG_OK; });
+}
+
+// The flags on the device (the lookups): t->gate (kNFlags ints, on first use) cleared on
+// the stream; the caller's checks, resolve and walk raise and read it with no host in
+// between; gate_end copies it to t->flags_host and is the call's one synchronisation.
+int gate_begin(psg_table* t, uint64_t n, hipStream_t st) {
+  PSG_TRY(ensure_slots(t, n));
+  if (!t->gate) PSG_HIP(hipMalloc((void**)&t->gate, kNFlags * sizeof(int)));
+  PSG_HIP(hipMemsetAsync(t->gate, 0, kNFlags * sizeof(int), st));
+  return PSG_OK;
+}
+int gate_end(psg_table* t, hipStream_t st) {
+  PSG_HIP(hipMemcpyAsync(t->flags_host, t->gate, kNFlags * sizeof(int), hipMemcpyDeviceToHost, st));
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
+int require_ascending(const psg_table* t) {
+  PSG_REQUIRE(!t->flags_host[R_UNSORTED], PSG_ERR_INVALID,
+              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
+  return PSG_OK;
+}
+
+int require_in_range(const psg_table* t) {
+  PSG_REQUIRE(!t->flags_host[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
+              (unsigned long long)t->key_begin, (unsigned long long)t->key_end);
+  return PSG_OK;
+}
+
+int require_offsets(const psg_table* t, const char* name, uint64_t n) {
+  PSG_REQUIRE(!t->flags_host[R_OFFSETS], PSG_ERR_INVALID,
+              "%s: offsets do not start at 0, ascend and end at n = %llu", name, (unsigned long long)n);
   return PSG_OK;
 }
 
@@ -1262,6 +1407,22 @@ struct DevBuf {  // a device scratch array freed on every return path
     if (p) (void)hipFree(p);
   }
 };
+
+// New arrays of `size` rows in `cap` take the table's place (insert, erase);
+// the old ones are left in K2 / R2 / M2 and freed with them.
+void publish_arrays(psg_table* t, DevBuf& K2, DevBuf& R2, DevBuf& M2, uint64_t size, uint64_t cap) {
+  void* old_keys = t->keys;
+  t->keys = (uint64_t*)K2.p;
+  K2.p = old_keys;
+  std::swap(R2.p, t->rows);
+  if (t->adam) {
+    void* old_mom = t->mom;
+    t->mom = (double*)M2.p;
+    M2.p = old_mom;
+  }
+  t->size = size;
+  t->capacity = cap;
+}
 
 // Insert the keys of q that t->slots marks absent, each with a zero row.
 int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) {
@@ -1289,63 +1450,35 @@ int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) 
   PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
   PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
   if (t->adam) PSG_HIP(hipMalloc(&M2.p, cap * mom_row_bytes(t)));
-  k_rows_merge_keys<<<grid_for((S + m + kBlock - 1) / kBlock), kBlock, 0, st>>>(
-      t->keys, S, (const uint64_t*)miss.p, m, (uint64_t*)K2.p, (uint32_t*)old_to.p, (uint32_t*)new_to.p);
+  k_rows_merge_keys<<<grid_per_lane(S + m), kBlock, 0, st>>>(t->keys, S, (const uint64_t*)miss.p, m, (uint64_t*)K2.p,
+                                                            (uint32_t*)old_to.p, (uint32_t*)new_to.p);
   PSG_HIP(hipGetLastError());
-  if (S) PSG_TRY(move_rows(t, t->rows, R2.p, (const uint32_t*)old_to.p, S, st));
-  PSG_TRY(move_rows(t, nullptr, R2.p, (const uint32_t*)new_to.p, m, st));
+  if (S) PSG_TRY(move_rows(t, false, t->rows, R2.p, (const uint32_t*)old_to.p, S, st));
+  PSG_TRY(move_rows(t, false, nullptr, R2.p, (const uint32_t*)new_to.p, m, st));
   if (t->adam) {  // the moment rows go where their value rows went: 2 * width doubles = width 16-B units
-    if (S) PSG_TRY(launch_move<u32x4>(t->mom, M2.p, (const uint32_t*)old_to.p, S, t->width, st));
-    PSG_TRY(launch_move<u32x4>(nullptr, M2.p, (const uint32_t*)new_to.p, m, t->width, st));
+    if (S) PSG_TRY(launch_move<u32x4>(false, t->mom, M2.p, (const uint32_t*)old_to.p, S, t->width, st));
+    PSG_TRY(launch_move<u32x4>(false, nullptr, M2.p, (const uint32_t*)new_to.p, m, t->width, st));
   }
   PSG_HIP(hipStreamSynchronize(st));
-  void* old_keys = t->keys;  // the old arrays are freed with K2 / R2
-  t->keys = (uint64_t*)K2.p;
-  K2.p = old_keys;
-  std::swap(R2.p, t->rows);
-  if (t->adam) {
-    void* old_mom = t->mom;
-    t->mom = (double*)M2.p;
-    M2.p = old_mom;
-  }
-  t->size = S + m;
-  t->capacity = cap;
+  publish_arrays(t, K2, R2, M2, S + m, cap);
   return PSG_OK;
 }
 
-// The front half of a request in three steps.  resolve_first: q into t->slots
-// and the request flags into t->flags_host; nothing is written to the table.
-int resolve_first(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
-  PSG_TRY(ensure_slots(t, n));
-  return resolve(t, keys, n, st);
-}
-
-int require_ascending(const psg_table* t) {
-  PSG_REQUIRE(!t->flags_host[R_UNSORTED], PSG_ERR_INVALID,
-              "request keys are not strictly ascending (KVPairs contract, KVApp.h:23)");
-  return PSG_OK;
-}
-
-int require_in_range(const psg_table* t) {
-  PSG_REQUIRE(!t->flags_host[R_RANGE], PSG_ERR_RANGE, "request key outside the table range [%llu, %llu)",
-              (unsigned long long)t->key_begin, (unsigned long long)t->key_end);
-  return PSG_OK;
-}
-
-// resolve_finish: a strictly ascending list in range — insert its absent keys.
+// Behind resolve_first's flags of a strictly ascending list in range: insert its
+// absent keys and resolve again.
 int resolve_finish(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
   if (t->flags_host[R_MISSING]) {
     PSG_TRY(insert_missing(t, keys, n, st));
-    PSG_TRY(resolve(t, keys, n, st));
+    PSG_TRY(resolve_first(t, keys, n, true, st));
     PSG_REQUIRE(!t->flags_host[R_MISSING], PSG_ERR_HIP, "psg_table: a key is absent after its insert");
   }
   return PSG_OK;
 }
 
-// The three in a row, as a strict call does them: a bad list is rejected before
+// The whole front half as a strict call does it: a bad list is rejected before
 // anything is written.  plan_any resolves its unique list this way.
 int resolve_request(psg_table* t, const uint64_t* keys, uint64_t n, hipStream_t st) {
-  PSG_TRY(resolve_first(t, keys, n, st));
+  PSG_TRY(resolve_first(t, keys, n, true, st));
   PSG_TRY(require_ascending(t));
   PSG_TRY(require_in_range(t));
   return resolve_finish(t, keys, n, st);
@@ -1380,6 +1513,28 @@ int any_scratch(psg_table* t, uint64_t n, AnyScratch* a) {
   a->seg = (uint32_t*)p, p += segb;
   a->counts = (uint32_t*)p;
   return PSG_OK;
+}
+
+// A key list into the sort's key buffer, `first` keys in (a round lays its frames' lists
+// end to end).  The sort permutes the buffer: a copy, the caller's keys are never written.
+int copy_keys(const AnyScratch& a, uint64_t first, const uint64_t* keys, uint64_t n, hipStream_t st) {
+  if (n) PSG_HIP(hipMemcpyAsync(a.k0 + first, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  return PSG_OK;
+}
+
+// A round's frame table before its k frames are filled in: from k on, offsets no position reaches.
+Frames round_frames(int k) {
+  Frames f = {};
+  f.k = k;
+  for (int j = k; j <= kMaxFrames; ++j) f.off[j] = 0xffffffffu;
+  return f;
+}
+
+// A frame's array of F32 rows moved back by the frame's first row in the round,
+// so that a row of the frames laid end to end indexes it as it is.
+template <typename T>
+T* moved_back(const psg_table* t, T* rows, uint32_t first) {
+  return (T*)((uintptr_t)rows - first * ((uint64_t)t->width * sizeof(float)));
 }
 
 int bit_width(uint64_t x) { return x ? 64 - __builtin_clzll(x) : 0; }
@@ -1417,8 +1572,7 @@ int plan_scratch(psg_table* t, const AnyScratch& a, uint64_t n, AnyPlan* plan, h
 int plan_any(psg_table* t, const uint64_t* keys, uint64_t n, AnyPlan* plan, hipStream_t st) {
   AnyScratch a;
   PSG_TRY(any_scratch(t, n, &a));
-  // the sort permutes its key buffer: a copy, the caller's keys are never written
-  PSG_HIP(hipMemcpyAsync(a.k0, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  PSG_TRY(copy_keys(a, 0, keys, n, st));
   return plan_scratch(t, a, n, plan, st);
 }
 
@@ -1429,15 +1583,13 @@ template <typename UNIT, int OP>
 int launch_walk(psg_table* t, const AnyPlan* p, const void* vals, void* out, uint64_t n, uint32_t upr,
                 const typename UNIT::Params& prm, hipStream_t st) {
   using U = typename UNIT::U;
-  const uint32_t rpt = rows_per_tile(upr);
-  const uint64_t rows = p ? p->m : n;
-  const unsigned g = grid_for((rows + rpt - 1) / rpt);
+  const Tiles g = tiles_for(p ? p->m : n, upr);
   if (p)
-    k_rows_walk_seg<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, (const U*)vals,
-                                                     (U*)out, rows, upr, rpt, prm);
+    k_rows_walk_seg<UNIT, OP><<<g.grid, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm,
+                                                          (const U*)vals, (U*)out, p->m, upr, g.rpt, prm);
   else
-    k_rows_walk<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, (const U*)vals, (U*)out, rows, upr, rpt,
-                                                 prm);
+    k_rows_walk<UNIT, OP><<<g.grid, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, (const U*)vals, (U*)out, n, upr,
+                                                      g.rpt, prm);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
@@ -1451,12 +1603,27 @@ int launch_op(psg_table* t, int op, const AnyPlan* p, const void* vals, void* ou
   return launch_walk<UNIT, PSG_PUSH | PSG_PULL>(t, p, vals, out, n, upr, prm, st);
 }
 
-// 16-B vectors when every row, here and in the request, starts on 16 B
-bool accumulate_vec(const psg_table* t, int op, const void* vals, const void* out) {
-  return ((uint64_t)t->width * t->esize) % 16 == 0 && (!(op & PSG_PUSH) || aligned16(vals)) &&
-         (!(op & PSG_PULL) || aligned16(out));
+// f(dt) with decltype(dt)::value the table's dtype
+template <typename F>
+int with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case PSG_F32: return f(std::integral_constant<int, PSG_F32>{});
+    case PSG_F64: return f(std::integral_constant<int, PSG_F64>{});
+    case PSG_F16: return f(std::integral_constant<int, PSG_F16>{});
+    default: return f(std::integral_constant<int, PSG_BF16>{});
+  }
 }
 
+int accumulate(psg_table* t, int op, const AnyPlan* p, const void* vals, void* out, uint64_t n, hipStream_t st) {
+  const bool vec = accumulate_vec(t, op, vals, out);
+  return with_dtype(t->dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (vec) return launch_op<AccUnit<DT, true>>(t, op, p, vals, out, n, t->width / Elem<DT>::kVec, {}, st);
+    return launch_op<AccUnit<DT, false>>(t, op, p, vals, out, n, t->width, {}, st);
+  });
+}
+
+// 16-B units of an update: four columns, every gradient and reply array on 16 B
 bool optimize_vec(const psg_table* t, int op, const float* grads, const float* out) {
   return t->width % 4 == 0 && aligned16(grads) && (!(op & PSG_PULL) || aligned16(out));
 }
@@ -1469,36 +1636,21 @@ AdamArgs adam_args(const psg_table* t, int iteration) {
           1 - std::pow(t->beta2, iteration + 1)};
 }
 
-template <int DT>
-int accumulate_dtype(psg_table* t, int op, const AnyPlan* p, const void* vals, void* out, uint64_t n, hipStream_t st) {
-  if (accumulate_vec(t, op, vals, out))
-    return launch_op<AccUnit<DT, true>>(t, op, p, vals, out, n, t->width / Elem<DT>::kVec, {}, st);
-  return launch_op<AccUnit<DT, false>>(t, op, p, vals, out, n, t->width, {}, st);
-}
-
-int accumulate(psg_table* t, int op, const AnyPlan* p, const void* vals, void* out, uint64_t n, hipStream_t st) {
-  switch (t->dtype) {
-    case PSG_F32: return accumulate_dtype<PSG_F32>(t, op, p, vals, out, n, st);
-    case PSG_F64: return accumulate_dtype<PSG_F64>(t, op, p, vals, out, n, st);
-    case PSG_F16: return accumulate_dtype<PSG_F16>(t, op, p, vals, out, n, st);
-    default: return accumulate_dtype<PSG_BF16>(t, op, p, vals, out, n, st);
-  }
-}
-
-template <bool ADAM>
-int optimize_adam(psg_table* t, int op, const AnyPlan* p, const float* grads, float* out, uint64_t n, float lr,
-                  int iteration, hipStream_t st) {
-  if (optimize_vec(t, op, grads, out))
-    return launch_op<OptUnit<ADAM, true>>(t, op, p, grads, out, n, t->width / 4,
-                                          {t->width, lr, adam_args(t, iteration)}, st);
-  return launch_op<OptUnit<ADAM, false>>(t, op, p, grads, out, n, t->width, {t->width, lr, adam_args(t, iteration)},
-                                         st);
-}
-
-int optimize(psg_table* t, int op, const AnyPlan* p, const float* grads, float* out, uint64_t n, float lr,
-             int iteration, hipStream_t st) {
-  return t->adam ? optimize_adam<true>(t, op, p, grads, out, n, lr, iteration, st)
-                 : optimize_adam<false>(t, op, p, grads, out, n, lr, iteration, st);
+// f(unit, upr, prm) for the table's optimizer unit: unit is a UnitTag of
+// OptUnit<ADAM, VEC> (ADAM: the table has Adam state; VEC: the caller's vec),
+// upr its units per row and prm its Params, built once for the request.
+template <typename UNIT> struct UnitTag {
+  using type = UNIT;
+};
+template <typename F>
+int with_opt_unit(const psg_table* t, bool vec, float lr, int iteration, F&& f) {
+  const AdamArgs a = adam_args(t, iteration);
+  auto with = [&](auto unit) {
+    using UNIT = typename decltype(unit)::type;
+    return f(unit, vec ? t->width / 4 : t->width, typename UNIT::Params{t->width, lr, a});
+  };
+  if (t->adam) return vec ? with(UnitTag<OptUnit<true, true>>{}) : with(UnitTag<OptUnit<true, false>>{});
+  return vec ? with(UnitTag<OptUnit<false, true>>{}) : with(UnitTag<OptUnit<false, false>>{});
 }
 
 // The body of the four request calls; `name` is the call's, for its messages.
@@ -1506,25 +1658,24 @@ int optimize(psg_table* t, int op, const AnyPlan* p, const float* grads, float* 
 // any: a list that is not strictly ascending is planned instead of rejected.
 int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const uint64_t* keys, const void* vals,
           void* out, uint64_t n, float lr, int iteration, psg_stream stream) {
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  PSG_TRY(require_table(name, t));
   if (opt) {
-    PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
-                "%s: flags %d are neither PUSH nor PUSH|PULL", name, flags);
-    PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
-    PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
+    PSG_TRY(require_update_flags(name, flags));
+    PSG_TRY(require_iteration(name, iteration));
+    PSG_TRY(require_f32(name, t));
   } else {
     PSG_REQUIRE(flags >= 1 && flags <= 3, PSG_ERR_INVALID, "%s: bad flags %d", name, flags);
   }
   if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
+  PSG_TRY(require_keys(name, keys));
   if (opt)
     PSG_REQUIRE(vals, PSG_ERR_INVALID, "%s: null grads", name);
   else
     PSG_REQUIRE(!(flags & PSG_PUSH) || vals, PSG_ERR_INVALID, "push without vals");
   PSG_REQUIRE(!(flags & PSG_PULL) || out, PSG_ERR_INVALID, "pull without out buffer");
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
+  PSG_TRY(require_count(name, n));
   hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(resolve_first(t, keys, n, st));
+  PSG_TRY(resolve_first(t, keys, n, true, st));
   // a strict call rejects a list out of order before it looks at the range
   if (!any) PSG_TRY(require_ascending(t));
   PSG_TRY(require_in_range(t));
@@ -1536,10 +1687,14 @@ int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const u
   } else {
     PSG_TRY(resolve_finish(t, keys, n, st));
   }
-  if (opt)
-    PSG_TRY(optimize(t, flags, p, (const float*)vals, (float*)out, n, lr, iteration, st));
-  else
+  if (opt) {
+    const bool vec = optimize_vec(t, flags, (const float*)vals, (const float*)out);
+    PSG_TRY(with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
+      return launch_op<typename decltype(unit)::type>(t, flags, p, vals, out, n, upr, prm, st);
+    }));
+  } else {
     PSG_TRY(accumulate(t, flags, p, vals, out, n, st));
+  }
   // complete on return: keys and vals no longer read, a Pull's reply in memory
   PSG_HIP(hipStreamSynchronize(st));
   return PSG_OK;
@@ -1552,234 +1707,52 @@ template <bool TO_TABLE>
 int move_moments(psg_table* t, const uint32_t* slots, uint64_t first, const double* m, const double* v, uint64_t n,
                  hipStream_t st) {
   const bool pair = t->width % 4 == 0 && aligned16(m) && aligned16(v);
-  const uint32_t upr = pair ? t->width : 2 * t->width;
-  const uint32_t rpt = rows_per_tile(upr);
-  const unsigned g = grid_for((n + rpt - 1) / rpt);
+  const Tiles g = tiles_for(n, pair ? t->width : 2 * t->width);
   double* mp = const_cast<double*>(m);
   double* vp = const_cast<double*>(v);
   if (pair)
-    k_mom_move<f64x2, TO_TABLE><<<g, kBlock, 0, st>>>(t->mom, slots, first, mp, vp, n, t->width, rpt);
+    k_mom_move<f64x2, TO_TABLE><<<g.grid, kBlock, 0, st>>>(t->mom, slots, first, mp, vp, n, t->width, g.rpt);
   else
-    k_mom_move<double, TO_TABLE><<<g, kBlock, 0, st>>>(t->mom, slots, first, mp, vp, n, t->width, rpt);
+    k_mom_move<double, TO_TABLE><<<g.grid, kBlock, 0, st>>>(t->mom, slots, first, mp, vp, n, t->width, g.rpt);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
 
 template <typename U>
 int launch_set(psg_table* t, const void* rows, uint64_t n, uint32_t upr, hipStream_t st) {
-  const uint32_t rpt = rows_per_tile(upr);
-  k_rows_walk<SetUnit<U>, PSG_PUSH><<<grid_for((n + rpt - 1) / rpt), kBlock, 0, st>>>(
-      (U*)t->rows, nullptr, t->slots, (const U*)rows, nullptr, n, upr, rpt, typename SetUnit<U>::Params{});
+  const Tiles g = tiles_for(n, upr);
+  k_rows_walk<SetUnit<U>, PSG_PUSH><<<g.grid, kBlock, 0, st>>>((U*)t->rows, nullptr, t->slots, (const U*)rows, nullptr,
+                                                               n, upr, g.rpt, typename SetUnit<U>::Params{});
   PSG_HIP(hipGetLastError());
-  return PSG_OK;
-}
-
-int assign(psg_table* t, const uint64_t* keys, const void* rows, const double* m, const double* v, uint64_t n,
-           psg_stream stream) {
-  const char* name = "psg_table_assign";
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
-  PSG_REQUIRE((m != nullptr) == (v != nullptr), PSG_ERR_INVALID, "%s: m and v come as a pair, %s is null", name,
-              m ? "v" : "m");
-  PSG_REQUIRE(!m || t->adam, PSG_ERR_INVALID, "%s: moments for a table without Adam state", name);
-  if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
-  PSG_REQUIRE(rows || !m, PSG_ERR_INVALID, "%s: moments without rows", name);
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
-  hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(resolve_request(t, keys, n, st));
-  // no rows: the list's absent keys are in the table now (one merge for a whole
-  // model, where assigning it chunk by chunk would merge once per chunk)
-  if (!rows) return PSG_OK;
-  // 16-B units under accumulate_vec's condition for a Push
-  if (accumulate_vec(t, PSG_PUSH, rows, nullptr))
-    PSG_TRY(launch_set<u32x4>(t, rows, n, t->width * (uint32_t)t->esize / 16, st));
-  else if (t->esize == 8)
-    PSG_TRY(launch_set<uint64_t>(t, rows, n, t->width, st));
-  else if (t->esize == 4)
-    PSG_TRY(launch_set<uint32_t>(t, rows, n, t->width, st));
-  else
-    PSG_TRY(launch_set<uint16_t>(t, rows, n, t->width, st));
-  if (m) PSG_TRY(move_moments<true>(t, t->slots, 0, m, v, n, st));
-  // complete on return: keys, rows, m and v are no longer read
-  PSG_HIP(hipStreamSynchronize(st));
-  return PSG_OK;
-}
-
-int export_rows(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out, void* rows_out, double* m_out,
-                double* v_out, psg_stream stream) {
-  const char* name = "psg_table_export";
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
-  PSG_REQUIRE((m_out != nullptr) == (v_out != nullptr), PSG_ERR_INVALID, "%s: m_out and v_out come as a pair, %s is null",
-              name, m_out ? "v_out" : "m_out");
-  PSG_REQUIRE(!m_out || t->adam, PSG_ERR_INVALID, "%s: moments of a table without Adam state", name);
-  PSG_REQUIRE(first <= t->size && count <= t->size - first, PSG_ERR_INVALID,
-              "%s: rows [%llu, %llu + %llu) of a table of %llu", name, (unsigned long long)first,
-              (unsigned long long)first, (unsigned long long)count, (unsigned long long)t->size);
-  if (count == 0) return PSG_OK;
-  PSG_REQUIRE(rows_out, PSG_ERR_INVALID, "%s: null rows_out", name);
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t row_bytes = (uint64_t)t->width * t->esize;
-  // keys and rows are in key order in the table: two copies inside HBM
-  if (keys_out)
-    PSG_HIP(hipMemcpyAsync(keys_out, t->keys + first, count * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-  PSG_HIP(hipMemcpyAsync(rows_out, (const char*)t->rows + first * row_bytes, count * row_bytes,
-                         hipMemcpyDeviceToDevice, st));
-  if (m_out) PSG_TRY(move_moments<false>(t, nullptr, first, m_out, v_out, count, st));
   return PSG_OK;
 }
 
 // ---- lookup and erase: the calls that never insert ---------------------------------
+// out null: presence alone, one lane per row
 template <typename U>
 int launch_read(psg_table* t, void* out, uint8_t* found, uint64_t n, uint32_t upr, hipStream_t st) {
-  const uint32_t rpt = rows_per_tile(upr);
-  const uint64_t blocks = out ? (n + rpt - 1) / rpt : (n + kBlock - 1) / kBlock;
-  k_rows_read<U><<<grid_for(blocks), kBlock, 0, st>>>((const U*)t->rows, t->slots, (U*)out, found, n, upr, rpt, t->gate);
+  const Tiles g = tiles_for(n, upr);
+  k_rows_read<U><<<out ? g.grid : grid_per_lane(n), kBlock, 0, st>>>((const U*)t->rows, t->slots, (U*)out, found, n, upr,
+                                                                    g.rpt, t->gate);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
 
-int lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* found, uint64_t n, psg_stream stream) {
-  const char* name = "psg_table_lookup";
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
-  if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
-  PSG_REQUIRE(out || found, PSG_ERR_INVALID, "%s: out and found are both null", name);
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
-  hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(ensure_slots(t, n));
-  if (!t->gate) PSG_HIP(hipMalloc((void**)&t->gate, kNFlags * sizeof(int)));
-  PSG_HIP(hipMemsetAsync(t->gate, 0, kNFlags * sizeof(int), st));
-  k_rows_resolve_any<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(keys, n, t->keys, t->size, t->key_begin,
-                                                                                  t->key_end, t->slots, t->gate);
-  PSG_HIP(hipGetLastError());
-  // 16-B units under accumulate_vec's condition for a Pull; presence alone has no unit
-  if (!out)
-    PSG_TRY(launch_read<u32x4>(t, nullptr, found, n, 1, st));
-  else if (accumulate_vec(t, PSG_PULL, nullptr, out))
-    PSG_TRY(launch_read<u32x4>(t, out, found, n, t->width * (uint32_t)t->esize / 16, st));
-  else if (t->esize == 8)
-    PSG_TRY(launch_read<uint64_t>(t, out, found, n, t->width, st));
-  else if (t->esize == 4)
-    PSG_TRY(launch_read<uint32_t>(t, out, found, n, t->width, st));
-  else
-    PSG_TRY(launch_read<uint16_t>(t, out, found, n, t->width, st));
-  // the one synchronisation: keys no longer read, the reply in memory, the flags on the host
-  PSG_HIP(hipMemcpyAsync(t->flags_host, t->gate, kNFlags * sizeof(int), hipMemcpyDeviceToHost, st));
-  PSG_HIP(hipStreamSynchronize(st));
-  return require_in_range(t);
-}
-
-template <typename U>
-int launch_take(const void* src, void* dst, const uint32_t* from, uint64_t nrows, uint32_t upr, hipStream_t st) {
-  const uint32_t rpt = rows_per_tile(upr);
-  k_rows_take<U><<<grid_for((nrows + rpt - 1) / rpt), kBlock, 0, st>>>((const U*)src, (U*)dst, from, nrows, upr, rpt);
-  PSG_HIP(hipGetLastError());
-  return PSG_OK;
-}
-
-// move_rows' units, gathered
-int take_rows(const psg_table* t, const void* src, void* dst, const uint32_t* from, uint64_t nrows, hipStream_t st) {
-  const uint32_t rb = t->width * (uint32_t)t->esize;
-  if (rb % 16 == 0) return launch_take<u32x4>(src, dst, from, nrows, rb / 16, st);
-  if (rb % 4 == 0) return launch_take<uint32_t>(src, dst, from, nrows, rb / 4, st);
-  return launch_take<uint16_t>(src, dst, from, nrows, rb / 2, st);
-}
-
-// insert_missing backwards: the slots the list names are marked dead, the
-// ordered compaction over the S slots gives the survivors' old slots, and keys,
-// rows and moment rows are gathered into new arrays that replace the old ones
-// after one synchronisation.
-int erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* erased_host, psg_stream stream) {
-  const char* name = "psg_table_erase";
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
-  if (erased_host) *erased_host = 0;
-  if (n == 0) return PSG_OK;
-  PSG_REQUIRE(keys, PSG_ERR_INVALID, "%s: null keys", name);
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
-  hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(ensure_slots(t, n));
-  memset(t->flags_host, 0, kNFlags * sizeof(int));
-  k_rows_resolve_any<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(keys, n, t->keys, t->size, t->key_begin,
-                                                                                  t->key_end, t->slots, t->flags);
-  PSG_HIP(hipGetLastError());
-  PSG_HIP(hipStreamSynchronize(st));
-  PSG_TRY(require_in_range(t));
-  const uint64_t S = t->size;
-  if (S == 0) return PSG_OK;
-  const uint64_t ntiles = compact_tiles(S);
-  DevBuf dead, counts, from;
-  PSG_HIP(hipMalloc(&dead.p, S));
-  PSG_HIP(hipMalloc(&counts.p, (ntiles + 1) * sizeof(uint32_t)));
-  PSG_HIP(hipMemsetAsync(dead.p, 0, S, st));
-  k_mark_dead<<<grid_for((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(t->slots, n, (uint8_t*)dead.p);
-  const Alive alive = {(const uint8_t*)dead.p};
-  compact_count(S, (uint32_t*)counts.p, alive, st);
-  PSG_HIP(hipGetLastError());
-  uint64_t m = 0;  // the survivors
-  PSG_TRY(read_count((const uint32_t*)counts.p + ntiles, &m, st));
-  PSG_REQUIRE(m <= S, PSG_ERR_HIP, "%s: %llu survivors of %llu rows", name, (unsigned long long)m, (unsigned long long)S);
-  if (m == S) return PSG_OK;  // no key of the list is present
-  DevBuf K2, R2, M2;
-  uint64_t cap = 0;
-  if (m) {
-    cap = std::max<uint64_t>(m, 1024);
-    const uint64_t row_bytes = (uint64_t)t->width * t->esize;
-    PSG_HIP(hipMalloc(&from.p, m * sizeof(uint32_t)));
-    PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
-    PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
-    if (t->adam) PSG_HIP(hipMalloc(&M2.p, cap * mom_row_bytes(t)));
-    compact_emit(S, (const uint32_t*)counts.p, alive, EmitSurvivor{t->keys, (uint64_t*)K2.p, (uint32_t*)from.p}, st);
-    PSG_HIP(hipGetLastError());
-    PSG_TRY(take_rows(t, t->rows, R2.p, (const uint32_t*)from.p, m, st));
-    // a moment row is 2 * width doubles = width 16-B units, as insert_missing moves it
-    if (t->adam) PSG_TRY(launch_take<u32x4>(t->mom, M2.p, (const uint32_t*)from.p, m, t->width, st));
-    PSG_HIP(hipStreamSynchronize(st));
-  }
-  // the old arrays are freed with K2 / R2 / M2; a table whose last key went keeps none
-  void* old_keys = t->keys;
-  t->keys = (uint64_t*)K2.p;
-  K2.p = old_keys;
-  std::swap(R2.p, t->rows);
-  if (t->adam) {
-    void* old_mom = t->mom;
-    t->mom = (double*)M2.p;
-    M2.p = old_mom;
-  }
-  t->size = m;
-  t->capacity = cap;
-  if (erased_host) *erased_host = S - m;
-  return PSG_OK;
-}
-
-// ---- the merged update: dispatch and body -----------------------------------------
+// ---- the merged update: dispatch --------------------------------------------------
 // The same-list walk over the n rows of list 0 (plan null), or the merge walk
 // over the plan's unique rows.
 template <typename UNIT, int OP>
 int launch_merged(psg_table* t, const AnyPlan* p, const Frames& f, uint64_t n, uint32_t upr,
                   const typename UNIT::Params& prm, hipStream_t st) {
   using U = typename UNIT::U;
-  const uint32_t rpt = rows_per_tile(upr);
-  const uint64_t rows = p ? p->m : n;
-  const unsigned g = grid_for((rows + rpt - 1) / rpt);
+  const Tiles g = tiles_for(p ? p->m : n, upr);
   if (p)
-    k_rows_walk_merge<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, f, rows, upr, rpt,
-                                                       prm);
+    k_rows_walk_merge<UNIT, OP><<<g.grid, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, f, p->m, upr,
+                                                            g.rpt, prm);
   else
-    k_rows_walk_same<UNIT, OP><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, f, rows, upr, rpt, prm);
+    k_rows_walk_same<UNIT, OP><<<g.grid, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, f, n, upr, g.rpt, prm);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
-}
-
-template <bool ADAM>
-int merged_adam(psg_table* t, int op, bool vec, const AnyPlan* p, const Frames& f, uint64_t n, float lr, int iteration,
-                hipStream_t st) {
-  const typename OptUnit<ADAM, true>::Params prm = {t->width, lr, adam_args(t, iteration)};
-  if (vec)
-    return op == PSG_PUSH ? launch_merged<OptUnit<ADAM, true>, PSG_PUSH>(t, p, f, n, t->width / 4, prm, st)
-                          : launch_merged<OptUnit<ADAM, true>, PSG_PUSH | PSG_PULL>(t, p, f, n, t->width / 4, prm, st);
-  const typename OptUnit<ADAM, false>::Params prm1 = {t->width, lr, prm.a};
-  return op == PSG_PUSH ? launch_merged<OptUnit<ADAM, false>, PSG_PUSH>(t, p, f, n, t->width, prm1, st)
-                        : launch_merged<OptUnit<ADAM, false>, PSG_PUSH | PSG_PULL>(t, p, f, n, t->width, prm1, st);
 }
 
 // Are the further key lists, over their first n keys, element for element list
@@ -1794,95 +1767,9 @@ int keys_differ(psg_table* t, int k, const uint64_t* const* keys, uint64_t n, bo
     any = any || keys[j] != keys[0];
   }
   if (!any) return PSG_OK;
-  k_keys_differ<<<grid_for((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(kf, n, order ? 1 : 0, t->flags);
+  k_keys_differ<<<grid_per_lane(n), kBlock, 0, st>>>(kf, n, order ? 1 : 0, t->flags);
   PSG_HIP(hipGetLastError());
   PSG_HIP(hipStreamSynchronize(st));
-  return PSG_OK;
-}
-
-int update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys, const uint64_t* ns,
-                  const float* const* grads, float* const* outs, float lr, int iteration, psg_stream stream,
-                  int* path_host) {
-  const char* name = "psg_table_update_merged";
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
-  PSG_REQUIRE(k >= 1 && k <= kMaxFrames, PSG_ERR_INVALID, "%s: %d frames outside [1, %d]", name, k, kMaxFrames);
-  PSG_REQUIRE(flags == PSG_PUSH || flags == (PSG_PUSH | PSG_PULL), PSG_ERR_INVALID,
-              "%s: flags %d are neither PUSH nor PUSH|PULL", name, flags);
-  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
-  PSG_REQUIRE(keys && ns && grads, PSG_ERR_INVALID, "%s: null keys, ns or grads array", name);
-  PSG_REQUIRE(!(flags & PSG_PULL) || outs, PSG_ERR_INVALID, "%s: pull without outs array", name);
-  const bool pull = (flags & PSG_PULL) != 0;
-  Frames f = {};
-  f.k = k;
-  uint64_t N = 0;
-  bool same = true;
-  bool vec = t->width % 4 == 0;
-  for (int j = 0; j < k; ++j) {
-    PSG_REQUIRE(ns[j] <= kMaxRows && N + ns[j] <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one round",
-                name);
-    f.off[j] = (uint32_t)N;
-    N += ns[j];
-    same = same && ns[j] == ns[0];
-    if (ns[j] == 0) continue;
-    PSG_REQUIRE(keys[j] && grads[j], PSG_ERR_INVALID, "%s: null keys or grads of frame %d", name, j);
-    PSG_REQUIRE(!pull || outs[j], PSG_ERR_INVALID, "%s: pull without out buffer of frame %d", name, j);
-    f.vals[j] = grads[j];
-    f.out[j] = pull ? outs[j] : nullptr;
-    vec = vec && aligned16(grads[j]) && (!pull || aligned16(outs[j]));  // optimize_vec's condition, every frame
-  }
-  for (int j = k; j <= kMaxFrames; ++j) f.off[j] = 0xffffffffu;
-  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
-  if (path_host) *path_host = 0;
-  if (N == 0) return PSG_OK;
-  hipStream_t st = (hipStream_t)stream;
-  // the same-list round: equal counts, list 0 strictly ascending, every list equal to it
-  const uint64_t n = ns[0];
-  if (same && k > 1) {
-    // the head of the lists first, one block: shuffled or differing lists are
-    // told apart here, for one small launch instead of a resolve of list 0
-    memset(t->flags_host, 0, kNFlags * sizeof(int));
-    PSG_TRY(keys_differ(t, k, keys, std::min<uint64_t>(n, kRowTile), true, st));
-    same = !t->flags_host[R_DIFFER];
-  }
-  bool resolved = false;  // t->flags_host holds the flags of the whole round's keys
-  if (same) {
-    PSG_TRY(resolve_first(t, keys[0], n, st));
-    resolved = k == 1;  // list 0 is the concatenation
-    same = !t->flags_host[R_UNSORTED];
-  }
-  if (same) {
-    PSG_TRY(require_in_range(t));
-    PSG_TRY(keys_differ(t, k, keys, n, false, st));
-    same = !t->flags_host[R_DIFFER];
-  }
-  AnyPlan plan;
-  const AnyPlan* p = nullptr;
-  if (same) {
-    PSG_TRY(resolve_finish(t, keys[0], n, st));
-  } else {
-    // the k lists one behind the other in the sort's key buffer; every key is
-    // checked against the range before the sort (and before the first write)
-    AnyScratch a;
-    PSG_TRY(any_scratch(t, N, &a));
-    for (int j = 0; j < k; ++j)
-      if (ns[j])
-        PSG_HIP(hipMemcpyAsync(a.k0 + f.off[j], keys[j], ns[j] * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    if (!resolved) PSG_TRY(resolve_first(t, a.k0, N, st));
-    PSG_TRY(require_in_range(t));
-    PSG_TRY(plan_scratch(t, a, N, &plan, st));
-    p = &plan;
-    // a position of the concatenation indexes a frame's arrays moved back by its offset
-    const uint64_t row_bytes = (uint64_t)t->width * sizeof(float);
-    for (int j = 0; j < k; ++j) {
-      if (f.vals[j]) f.vals[j] = (const void*)((uintptr_t)f.vals[j] - f.off[j] * row_bytes);
-      if (f.out[j]) f.out[j] = (void*)((uintptr_t)f.out[j] - f.off[j] * row_bytes);
-    }
-  }
-  PSG_TRY(t->adam ? merged_adam<true>(t, flags, vec, p, f, n, lr, iteration, st)
-                  : merged_adam<false>(t, flags, vec, p, f, n, lr, iteration, st));
-  // complete on return: keys and grads no longer read, the replies in memory
-  PSG_HIP(hipStreamSynchronize(st));
-  if (path_host) *path_host = same ? PSG_MERGED_SAME_LIST : PSG_MERGED_SORTED;
   return PSG_OK;
 }
 
@@ -1891,24 +1778,12 @@ int update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys, c
 // forward's out or the backward's grads.
 int pooled_args(const char* name, const psg_table* t, const uint64_t* keys, const uint64_t* offsets, const void* rows,
                 const char* rows_name, uint64_t n, uint64_t nb) {
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
+  PSG_TRY(require_table(name, t));
   PSG_REQUIRE(keys || n == 0, PSG_ERR_INVALID, "%s: null keys", name);
   PSG_REQUIRE(offsets || nb == 0, PSG_ERR_INVALID, "%s: null offsets", name);
   PSG_REQUIRE(rows || nb == 0, PSG_ERR_INVALID, "%s: null %s", name, rows_name);
   PSG_REQUIRE(nb > 0 || n == 0, PSG_ERR_INVALID, "%s: %llu keys and no bag to hold them", name,
               (unsigned long long)n);
-  return PSG_OK;
-}
-
-int require_offsets(const psg_table* t, const char* name, uint64_t n) {
-  PSG_REQUIRE(!t->flags_host[R_OFFSETS], PSG_ERR_INVALID,
-              "%s: offsets do not start at 0, ascend and end at n = %llu", name, (unsigned long long)n);
-  return PSG_OK;
-}
-
-int launch_offsets_check(const uint64_t* offsets, uint64_t n, uint64_t nb, int* flags, hipStream_t st) {
-  k_offsets_check<<<grid_for((nb + kBlock) / kBlock), kBlock, 0, st>>>(offsets, nb, n, flags);
-  PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
 
@@ -1929,79 +1804,62 @@ int launch_pool(psg_table* t, const uint64_t* offsets, const float* weights, int
                 uint32_t upr, hipStream_t st) {
   using ACC = PoolAcc<DT, VEC>;
   using U = typename ACC::U;
-  const uint32_t rpt = rows_per_tile(upr);
-  const unsigned g = grid_for((nb + rpt - 1) / rpt);
+  const Tiles g = tiles_for(nb, upr);
   if (pool == kPoolWeighted)
-    k_rows_pool<U, ACC, kPoolWeighted><<<g, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr, rpt,
-                                                             t->gate, weights);
+    k_rows_pool<U, ACC, kPoolWeighted><<<g.grid, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr,
+                                                                  g.rpt, t->gate, weights);
   else if (pool == kPoolMean)
-    k_rows_pool<U, ACC, kPoolMean><<<g, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr, rpt,
-                                                         t->gate);
+    k_rows_pool<U, ACC, kPoolMean><<<g.grid, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr,
+                                                              g.rpt, t->gate);
   else
-    k_rows_pool<U, ACC><<<g, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr, rpt, t->gate);
+    k_rows_pool<U, ACC><<<g.grid, kBlock, 0, st>>>((const U*)t->rows, t->slots, offsets, (U*)out, nb, upr, g.rpt,
+                                                   t->gate);
   PSG_HIP(hipGetLastError());
   return PSG_OK;
-}
-
-template <int DT>
-int pool_dtype(psg_table* t, const uint64_t* offsets, const float* weights, int pool, void* out, uint64_t nb,
-               hipStream_t st) {
-  // 16-B units under accumulate_vec's condition for a Pull (the weights are read as words either way)
-  if (accumulate_vec(t, PSG_PULL, nullptr, out))
-    return launch_pool<DT, true>(t, offsets, weights, pool, out, nb, t->width / Elem<DT>::kVec, st);
-  return launch_pool<DT, false>(t, offsets, weights, pool, out, nb, t->width, st);
 }
 
 int lookup_pooled(const char* name, psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* weights,
                   int mode, void* out, uint64_t n, uint64_t nb, psg_stream stream) {
   PSG_TRY(pooled_args(name, t, keys, offsets, out, "out", n, nb));
   PSG_TRY(pool_mode_args(name, weights, mode));
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
-  PSG_REQUIRE(nb <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 bags in one request", name);
+  PSG_TRY(require_count(name, n));
+  PSG_TRY(require_count(name, nb, "bags"));
   if (nb == 0) return PSG_OK;
   hipStream_t st = (hipStream_t)stream;
-  PSG_TRY(ensure_slots(t, n));
-  if (!t->gate) PSG_HIP(hipMalloc((void**)&t->gate, kNFlags * sizeof(int)));
-  PSG_HIP(hipMemsetAsync(t->gate, 0, kNFlags * sizeof(int), st));
+  PSG_TRY(gate_begin(t, n, st));
   PSG_TRY(launch_offsets_check(offsets, n, nb, t->gate, st));
-  if (n) {
-    k_rows_resolve_any<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(
-        keys, n, t->keys, t->size, t->key_begin, t->key_end, t->slots, t->gate);
-    PSG_HIP(hipGetLastError());
-  }
+  if (n) PSG_TRY(launch_resolve(t, keys, n, t->gate, false, st));
   const int pool = mode == PSG_POOL_MEAN ? kPoolMean : weights ? kPoolWeighted : kPoolSum;
-  switch (t->dtype) {
-    case PSG_F32: PSG_TRY(pool_dtype<PSG_F32>(t, offsets, weights, pool, out, nb, st)); break;
-    case PSG_F64: PSG_TRY(pool_dtype<PSG_F64>(t, offsets, weights, pool, out, nb, st)); break;
-    case PSG_F16: PSG_TRY(pool_dtype<PSG_F16>(t, offsets, weights, pool, out, nb, st)); break;
-    default: PSG_TRY(pool_dtype<PSG_BF16>(t, offsets, weights, pool, out, nb, st)); break;
-  }
+  // 16-B units under accumulate_vec's condition for a Pull (the weights are read as words either way)
+  const bool vec = accumulate_vec(t, PSG_PULL, nullptr, out);
+  PSG_TRY(with_dtype(t->dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (vec) return launch_pool<DT, true>(t, offsets, weights, pool, out, nb, t->width / Elem<DT>::kVec, st);
+    return launch_pool<DT, false>(t, offsets, weights, pool, out, nb, t->width, st);
+  }));
   // the one synchronisation: keys, offsets and weights no longer read, the reply in memory, the flags on the host
-  PSG_HIP(hipMemcpyAsync(t->flags_host, t->gate, kNFlags * sizeof(int), hipMemcpyDeviceToHost, st));
-  PSG_HIP(hipStreamSynchronize(st));
+  PSG_TRY(gate_end(t, st));
   PSG_TRY(require_offsets(t, name, n));
   return require_in_range(t);
 }
 
-// The pooled walk for one unit type: over the plan's unique rows, their gradient
-// rows in the one array `grads` or (f not null, always with a plan) in the
-// round's frames; without a plan the strict walk over the list's n rows.
-// The weighted or the mean walk (src: WeightedArray / MeanArray) over the plan's
-// unique rows with bags[p] the gradient row of sorted position p, or without a
-// plan the strict walk with bags = bag_of.
+// The pooled walk for one unit type and one source of gradient rows (src:
+// OneArray, WeightedArray, MeanArray or, always with a plan, FrameArrays): over
+// the plan's unique rows with bags[p] the gradient row of sorted position p, or
+// without a plan the strict walk over the list's n rows with bags = bag_of.
 template <typename UNIT, typename SRC>
-int launch_walk_scaled(psg_table* t, const AnyPlan* p, const uint32_t* bags, const SRC& src, uint64_t n, uint32_t upr,
-                       const typename UNIT::Params& prm, hipStream_t st) {
+int launch_walk_src(psg_table* t, const AnyPlan* p, const uint32_t* bags, const SRC& src, uint64_t n, uint32_t upr,
+                    const typename UNIT::Params& prm, hipStream_t st) {
   using U = typename UNIT::U;
-  const uint32_t rpt = rows_per_tile(upr);
-  const uint64_t rows = p ? p->m : n;
-  const unsigned g = grid_for((rows + rpt - 1) / rpt);
-  if (p)
-    k_rows_walk_pool<UNIT, SRC, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, bags, src, rows, upr,
-                                                             rpt, prm);
-  else
-    k_rows_walk_pool<UNIT, SRC, true><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, nullptr, bags, src, rows, upr,
-                                                            rpt, prm);
+  if constexpr (SRC::kFrames) PSG_REQUIRE(p, PSG_ERR_INVALID, "psg_table: a round of frames without a plan");
+  const Tiles g = tiles_for(p ? p->m : n, upr);
+  if (p) {
+    k_rows_walk_pool<UNIT, SRC, false><<<g.grid, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, bags, src, p->m,
+                                                                  upr, g.rpt, prm);
+  } else if constexpr (!SRC::kFrames) {
+    k_rows_walk_pool<UNIT, SRC, true><<<g.grid, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, nullptr, bags, src, n, upr,
+                                                                 g.rpt, prm);
+  }
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
@@ -2014,41 +1872,25 @@ struct PoolScale {
   const uint64_t* offsets;
 };
 
+// The gradient rows in the round's frames (f not null: always a plan, no scale) or in the
+// one array `grads`; bags: the walk's row indices where the sort did not carry them (p->perm).
 template <typename UNIT>
-int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bag_of, const float* grads, const Frames* f,
+int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bags, const float* grads, const Frames* f,
                      const PoolScale& sc, uint64_t n, uint32_t upr, const typename UNIT::Params& prm, hipStream_t st) {
   using U = typename UNIT::U;
-  if (sc.weights)
-    return launch_walk_scaled<UNIT>(t, p, bag_of, WeightedArray<U>{(const U*)grads, sc.weights}, n, upr, prm, st);
-  if (sc.offsets)
-    return launch_walk_scaled<UNIT>(t, p, p ? p->perm : bag_of, MeanArray<U>{(const U*)grads, sc.offsets}, n, upr, prm,
-                                    st);
-  const uint32_t rpt = rows_per_tile(upr);
-  const uint64_t rows = p ? p->m : n;
-  const unsigned g = grid_for((rows + rpt - 1) / rpt);
-  const OneArray<U> one = {(const U*)grads};
-  if (f)
-    k_rows_walk_pool<UNIT, FrameArrays, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm,
-                                                                     FrameArrays{*f}, rows, upr, rpt, prm);
-  else if (p)
-    k_rows_walk_pool<UNIT, OneArray<U>, false><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, p->seg, p->perm, one,
-                                                                     rows, upr, rpt, prm);
-  else
-    k_rows_walk_pool<UNIT, OneArray<U>, true><<<g, kBlock, 0, st>>>((U*)t->rows, t->mom, t->slots, nullptr, bag_of, one,
-                                                                    rows, upr, rpt, prm);
-  PSG_HIP(hipGetLastError());
-  return PSG_OK;
+  if (f) return launch_walk_src<UNIT>(t, p, p->perm, FrameArrays{*f}, n, upr, prm, st);
+  if (sc.weights) return launch_walk_src<UNIT>(t, p, bags, WeightedArray<U>{(const U*)grads, sc.weights}, n, upr, prm, st);
+  if (p) bags = p->perm;
+  if (sc.offsets) return launch_walk_src<UNIT>(t, p, bags, MeanArray<U>{(const U*)grads, sc.offsets}, n, upr, prm, st);
+  return launch_walk_src<UNIT>(t, p, bags, OneArray<U>{(const U*)grads}, n, upr, prm, st);
 }
 
 // vec: 16-B units (optimize_vec's condition for a Push, on every gradient array)
-template <bool ADAM>
-int pooled_adam(psg_table* t, bool vec, const AnyPlan* p, const uint32_t* bag_of, const float* grads, const Frames* f,
+int pooled_step(psg_table* t, bool vec, const AnyPlan* p, const uint32_t* bags, const float* grads, const Frames* f,
                 const PoolScale& sc, uint64_t n, float lr, int iteration, hipStream_t st) {
-  if (vec)
-    return launch_walk_pool<OptUnit<ADAM, true>>(t, p, bag_of, grads, f, sc, n, t->width / 4,
-                                                 {t->width, lr, adam_args(t, iteration)}, st);
-  return launch_walk_pool<OptUnit<ADAM, false>>(t, p, bag_of, grads, f, sc, n, t->width,
-                                                {t->width, lr, adam_args(t, iteration)}, st);
+  return with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
+    return launch_walk_pool<typename decltype(unit)::type>(t, p, bags, grads, f, sc, n, upr, prm, st);
+  });
 }
 
 // bags[p] = bag_of[perm[p]] and w[p] = weights[perm[p]] for p < n: the weighted
@@ -2075,23 +1917,15 @@ int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
                   int* path) {
   PSG_TRY(pooled_args(name, t, keys, offsets, grads, "grads", n, nb));
   PSG_TRY(pool_mode_args(name, weights, mode));
-  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
-  PSG_REQUIRE(n <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one request", name);
-  PSG_REQUIRE(nb <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 bags in one request", name);
-  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
+  PSG_TRY(require_iteration(name, iteration));
+  PSG_TRY(require_count(name, n));
+  PSG_TRY(require_count(name, nb, "bags"));
+  PSG_TRY(require_f32(name, t));
   if (nb == 0) return PSG_OK;
   hipStream_t st = (hipStream_t)stream;
-  // resolve_first with the offsets check in front of it: both raise their flags
-  // in t->flags_host, read after one synchronisation; nothing is written yet
-  PSG_TRY(ensure_slots(t, n));
-  memset(t->flags_host, 0, kNFlags * sizeof(int));
-  PSG_TRY(launch_offsets_check(offsets, n, nb, t->flags, st));
-  if (n) {
-    k_rows_resolve<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(keys, n, t->keys, t->size, t->key_begin,
-                                                                              t->key_end, t->slots, t->flags);
-    PSG_HIP(hipGetLastError());
-  }
-  PSG_HIP(hipStreamSynchronize(st));
+  // the offsets check in front of the resolve: both raise their flags in
+  // t->flags_host, read after one synchronisation; nothing is written yet
+  PSG_TRY(resolve_first(t, keys, n, true, st, [&] { return launch_offsets_check(offsets, n, nb, t->flags, st); }));
   PSG_TRY(require_offsets(t, name, n));
   PSG_TRY(require_in_range(t));
   if (n == 0) return PSG_OK;  // every bag is empty: no gradient row is read
@@ -2106,7 +1940,7 @@ int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
   const uint32_t* bags = a.p0;  // what the walk reads at its positions (sorted path, unweighted: plan.perm)
   PoolScale sc = {weights, mode == PSG_POOL_MEAN ? offsets : nullptr};
   if (!by_position) {
-    k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, 0, a.p0);
+    k_bag_of<<<grid_per_lane(nb), kBlock, 0, st>>>(offsets, nb, 0, a.p0);
     PSG_HIP(hipGetLastError());
   }
   AnyPlan plan;
@@ -2114,7 +1948,7 @@ int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
   if (strict) {
     PSG_TRY(resolve_finish(t, keys, n, st));
   } else {
-    PSG_HIP(hipMemcpyAsync(a.k0, keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    PSG_TRY(copy_keys(a, 0, keys, n, st));
     PSG_TRY(plan_scratch(t, a, n, &plan, st, !by_position));
     p = &plan;
   }
@@ -2125,116 +1959,18 @@ int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
     uint32_t* bag_of = plan.perm == a.p0 ? a.p1 : a.p0;
     uint32_t* sorted_bags = (uint32_t*)a.k0;
     float* sorted_w = (float*)(sorted_bags + n);
-    k_bag_of<<<grid_for((nb + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets, nb, 0, bag_of);
+    k_bag_of<<<grid_per_lane(nb), kBlock, 0, st>>>(offsets, nb, 0, bag_of);
     PSG_HIP(hipGetLastError());
-    k_pool_gather<<<grid_for((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(plan.perm, bag_of, weights, sorted_bags,
-                                                                          sorted_w, n);
+    k_pool_gather<<<grid_per_lane(n), kBlock, 0, st>>>(plan.perm, bag_of, weights, sorted_bags, sorted_w, n);
     PSG_HIP(hipGetLastError());
     bags = sorted_bags;
     sc.weights = sorted_w;
   }
   const bool vec = optimize_vec(t, PSG_PUSH, grads, nullptr);
-  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, p, bags, grads, nullptr, sc, n, lr, iteration, st)
-                  : pooled_adam<false>(t, vec, p, bags, grads, nullptr, sc, n, lr, iteration, st));
+  PSG_TRY(pooled_step(t, vec, p, bags, grads, nullptr, sc, n, lr, iteration, st));
   // complete on return: keys, offsets, weights and grads no longer read
   PSG_HIP(hipStreamSynchronize(st));
   if (path) *path = strict ? PSG_MERGED_SAME_LIST : PSG_MERGED_SORTED;
-  return PSG_OK;
-}
-
-// ---- the round of pooled and plain frames (psg_table_update_pooled_merged) ---------
-// update_merged's sorted path with update_pooled's payload: the k key lists one
-// behind the other in the sort's key buffer and, in its payload buffer, every
-// occurrence's gradient row in the frames' gradient arrays laid end to end
-// (k_row_index for a plain frame, k_bag_of for a pooled one, each from its
-// frame's first row).  A round of plain frames is update_merged's, one pooled
-// frame is update_pooled's.
-int update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys, const uint64_t* ns,
-                         const uint64_t* const* offsets, const uint64_t* nbs, const float* const* grads, float lr,
-                         int iteration, psg_stream stream, int* path_host) {
-  const char* name = "psg_table_update_pooled_merged";
-  PSG_REQUIRE(t, PSG_ERR_INVALID, "%s: null table", name);
-  PSG_REQUIRE(k >= 1 && k <= kMaxFrames, PSG_ERR_INVALID, "%s: %d frames outside [1, %d]", name, k, kMaxFrames);
-  PSG_REQUIRE(iteration >= 0, PSG_ERR_INVALID, "%s: iteration %d below 0", name, iteration);
-  PSG_REQUIRE(keys && ns && offsets && nbs && grads, PSG_ERR_INVALID, "%s: null keys, ns, offsets, nbs or grads array",
-              name);
-  bool pooled = false;
-  for (int j = 0; j < k; ++j) {
-    PSG_REQUIRE(keys[j] || ns[j] == 0, PSG_ERR_INVALID, "%s: null keys of frame %d", name, j);
-    if (offsets[j]) {
-      pooled = true;
-      PSG_REQUIRE(grads[j] || nbs[j] == 0, PSG_ERR_INVALID, "%s: null grads of pooled frame %d", name, j);
-      PSG_REQUIRE(nbs[j] > 0 || ns[j] == 0, PSG_ERR_INVALID, "%s: %llu keys of frame %d and no bag to hold them", name,
-                  (unsigned long long)ns[j], j);
-    } else {
-      PSG_REQUIRE(grads[j] || ns[j] == 0, PSG_ERR_INVALID, "%s: null grads of frame %d", name, j);
-    }
-  }
-  Frames f = {};  // off: the first gradient row of each frame
-  f.k = k;
-  uint32_t koff[kMaxFrames];  // the first key of each frame in the concatenation
-  uint64_t N = 0, G = 0;
-  for (int j = 0; j < k; ++j) {
-    const uint64_t g = offsets[j] ? nbs[j] : ns[j];
-    PSG_REQUIRE(ns[j] <= kMaxRows && N + ns[j] <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 keys in one round", name);
-    PSG_REQUIRE(g <= kMaxRows && G + g <= kMaxRows, PSG_ERR_RANGE, "%s: more than 2^32-2 gradient rows in one round",
-                name);
-    koff[j] = (uint32_t)N;
-    f.off[j] = (uint32_t)G;
-    N += ns[j];
-    G += g;
-  }
-  for (int j = k; j <= kMaxFrames; ++j) f.off[j] = 0xffffffffu;
-  PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
-  if (path_host) *path_host = 0;
-  if (!pooled) return update_merged(t, PSG_PUSH, k, keys, ns, grads, nullptr, lr, iteration, stream, path_host);
-  if (k == 1) return update_pooled(name, t, keys[0], offsets[0], nullptr, PSG_POOL_SUM, grads[0], ns[0], nbs[0], lr, iteration, stream,
-                         path_host);
-  if (N == 0 && G == 0) return PSG_OK;  // no key and no bag: nothing to check either
-  hipStream_t st = (hipStream_t)stream;
-  // the front half: every offsets array checked before anything else reads it,
-  // every key against the range; one synchronisation, nothing written yet
-  AnyScratch a = {};
-  if (N) {
-    PSG_TRY(ensure_slots(t, N));
-    PSG_TRY(any_scratch(t, N, &a));
-  }
-  memset(t->flags_host, 0, kNFlags * sizeof(int));
-  for (int j = 0; j < k; ++j) {
-    if (offsets[j] && nbs[j]) PSG_TRY(launch_offsets_check(offsets[j], ns[j], nbs[j], t->flags, st));
-    if (ns[j]) PSG_HIP(hipMemcpyAsync(a.k0 + koff[j], keys[j], ns[j] * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-  }
-  if (N) {
-    k_rows_resolve<<<grid_for((N + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(a.k0, N, t->keys, t->size, t->key_begin,
-                                                                              t->key_end, t->slots, t->flags);
-    PSG_HIP(hipGetLastError());
-  }
-  PSG_HIP(hipStreamSynchronize(st));
-  PSG_REQUIRE(!t->flags_host[R_OFFSETS], PSG_ERR_INVALID,
-              "%s: the offsets of a pooled frame do not start at 0, ascend and end at its ns", name);
-  PSG_TRY(require_in_range(t));
-  if (N == 0) return PSG_OK;  // every frame is empty: no gradient row is read
-  // the payload, and each frame's array moved back by its first row; 16-B units
-  // under optimize_vec's condition on every array that is read
-  bool vec = t->width % 4 == 0;
-  const uint64_t row_bytes = (uint64_t)t->width * sizeof(float);
-  for (int j = 0; j < k; ++j) {
-    if (ns[j] == 0) continue;
-    if (offsets[j])
-      k_bag_of<<<grid_for((nbs[j] + kBlock - 1) / kBlock), kBlock, 0, st>>>(offsets[j], nbs[j], f.off[j], a.p0 + koff[j]);
-    else
-      k_row_index<<<grid_for((ns[j] + kBlock - 1) / kBlock), kBlock, 0, st>>>(a.p0 + koff[j], ns[j], f.off[j]);
-    PSG_HIP(hipGetLastError());
-    vec = vec && aligned16(grads[j]);
-    f.vals[j] = (const void*)((uintptr_t)grads[j] - f.off[j] * row_bytes);
-  }
-  AnyPlan plan;
-  PSG_TRY(plan_scratch(t, a, N, &plan, st, true));
-  PSG_TRY(t->adam ? pooled_adam<true>(t, vec, &plan, nullptr, nullptr, &f, {}, N, lr, iteration, st)
-                  : pooled_adam<false>(t, vec, &plan, nullptr, nullptr, &f, {}, N, lr, iteration, st));
-  // complete on return: keys, offsets and grads no longer read
-  PSG_HIP(hipStreamSynchronize(st));
-  if (path_host) *path_host = PSG_MERGED_SORTED;
   return PSG_OK;
 }
 
@@ -2371,10 +2107,87 @@ int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const fl
   return serve("psg_table_update_any", true, true, t, flags, keys, grads, out, n, lr, iteration, stream);
 }
 
-int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys_host, const uint64_t* ns_host,
-                            const float* const* grads_host, float* const* outs_host, float lr, int iteration,
-                            psg_stream stream, int* path_host) {
-  return update_merged(t, flags, k, keys_host, ns_host, grads_host, outs_host, lr, iteration, stream, path_host);
+// ---- the merged update ------------------------------------------------------------
+int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* const* keys, const uint64_t* ns,
+                            const float* const* grads, float* const* outs, float lr, int iteration, psg_stream stream,
+                            int* path_host) {
+  const char* name = "psg_table_update_merged";
+  PSG_TRY(require_table(name, t));
+  PSG_TRY(require_frame_count(name, k));
+  PSG_TRY(require_update_flags(name, flags));
+  PSG_TRY(require_iteration(name, iteration));
+  PSG_REQUIRE(keys && ns && grads, PSG_ERR_INVALID, "%s: null keys, ns or grads array", name);
+  PSG_REQUIRE(!(flags & PSG_PULL) || outs, PSG_ERR_INVALID, "%s: pull without outs array", name);
+  const bool pull = (flags & PSG_PULL) != 0;
+  Frames f = round_frames(k);
+  uint64_t N = 0;
+  bool same = true;
+  bool vec = t->width % 4 == 0;
+  for (int j = 0; j < k; ++j) {
+    PSG_TRY(require_round_count(name, N, ns[j]));
+    f.off[j] = (uint32_t)N;
+    N += ns[j];
+    same = same && ns[j] == ns[0];
+    if (ns[j] == 0) continue;
+    PSG_REQUIRE(keys[j] && grads[j], PSG_ERR_INVALID, "%s: null keys or grads of frame %d", name, j);
+    PSG_REQUIRE(!pull || outs[j], PSG_ERR_INVALID, "%s: pull without out buffer of frame %d", name, j);
+    f.vals[j] = grads[j];
+    f.out[j] = pull ? outs[j] : nullptr;
+    vec = vec && aligned16(grads[j]) && (!pull || aligned16(outs[j]));  // optimize_vec's condition, every frame
+  }
+  PSG_TRY(require_f32(name, t));
+  if (path_host) *path_host = 0;
+  if (N == 0) return PSG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // the same-list round: equal counts, list 0 strictly ascending, every list equal to it
+  const uint64_t n = ns[0];
+  if (same && k > 1) {
+    // the head of the lists first, one block: shuffled or differing lists are
+    // told apart here, for one small launch instead of a resolve of list 0
+    memset(t->flags_host, 0, kNFlags * sizeof(int));
+    PSG_TRY(keys_differ(t, k, keys, std::min<uint64_t>(n, kRowTile), true, st));
+    same = !t->flags_host[R_DIFFER];
+  }
+  bool resolved = false;  // t->flags_host holds the flags of the whole round's keys
+  if (same) {
+    PSG_TRY(resolve_first(t, keys[0], n, true, st));
+    resolved = k == 1;  // list 0 is the concatenation
+    same = !t->flags_host[R_UNSORTED];
+  }
+  if (same) {
+    PSG_TRY(require_in_range(t));
+    PSG_TRY(keys_differ(t, k, keys, n, false, st));
+    same = !t->flags_host[R_DIFFER];
+  }
+  AnyPlan plan;
+  const AnyPlan* p = nullptr;
+  if (same) {
+    PSG_TRY(resolve_finish(t, keys[0], n, st));
+  } else {
+    // the k lists one behind the other in the sort's key buffer; every key is
+    // checked against the range before the sort (and before the first write)
+    AnyScratch a;
+    PSG_TRY(any_scratch(t, N, &a));
+    for (int j = 0; j < k; ++j) PSG_TRY(copy_keys(a, f.off[j], keys[j], ns[j], st));
+    if (!resolved) PSG_TRY(resolve_first(t, a.k0, N, true, st));
+    PSG_TRY(require_in_range(t));
+    PSG_TRY(plan_scratch(t, a, N, &plan, st));
+    p = &plan;
+    // a position of the concatenation indexes a frame's arrays moved back by its offset
+    for (int j = 0; j < k; ++j) {
+      if (f.vals[j]) f.vals[j] = moved_back(t, f.vals[j], f.off[j]);
+      if (f.out[j]) f.out[j] = moved_back(t, f.out[j], f.off[j]);
+    }
+  }
+  PSG_TRY(with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
+    using UNIT = typename decltype(unit)::type;
+    return flags == PSG_PUSH ? launch_merged<UNIT, PSG_PUSH>(t, p, f, n, upr, prm, st)
+                             : launch_merged<UNIT, PSG_PUSH | PSG_PULL>(t, p, f, n, upr, prm, st);
+  }));
+  // complete on return: keys and grads no longer read, the replies in memory
+  PSG_HIP(hipStreamSynchronize(st));
+  if (path_host) *path_host = same ? PSG_MERGED_SAME_LIST : PSG_MERGED_SORTED;
+  return PSG_OK;
 }
 
 int psg_table_get_adam(psg_table* t, int* has_adam, double* params4) {
@@ -2384,24 +2197,128 @@ int psg_table_get_adam(psg_table* t, int* has_adam, double* params4) {
   return PSG_OK;
 }
 
+// ---- assign and export ------------------------------------------------------------
 int psg_table_assign(psg_table* t, const uint64_t* keys, const void* rows, const double* m, const double* v,
                      uint64_t n, psg_stream stream) {
-  return assign(t, keys, rows, m, v, n, stream);
+  const char* name = "psg_table_assign";
+  PSG_TRY(require_table(name, t));
+  PSG_REQUIRE((m != nullptr) == (v != nullptr), PSG_ERR_INVALID, "%s: m and v come as a pair, %s is null", name,
+              m ? "v" : "m");
+  PSG_REQUIRE(!m || t->adam, PSG_ERR_INVALID, "%s: moments for a table without Adam state", name);
+  if (n == 0) return PSG_OK;
+  PSG_TRY(require_keys(name, keys));
+  PSG_REQUIRE(rows || !m, PSG_ERR_INVALID, "%s: moments without rows", name);
+  PSG_TRY(require_count(name, n));
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(resolve_request(t, keys, n, st));
+  // no rows: the list's absent keys are in the table now (one merge for a whole
+  // model, where assigning it chunk by chunk would merge once per chunk)
+  if (!rows) return PSG_OK;
+  const uint32_t row_bytes = t->width * (uint32_t)t->esize;
+  PSG_TRY(for_raw_unit(request_unit_bytes(t, PSG_PUSH, rows, nullptr), [&](auto u) {
+    return launch_set<decltype(u)>(t, rows, n, row_bytes / (uint32_t)sizeof(u), st);
+  }));
+  if (m) PSG_TRY(move_moments<true>(t, t->slots, 0, m, v, n, st));
+  // complete on return: keys, rows, m and v are no longer read
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
 }
 
 int psg_table_export(psg_table* t, uint64_t first, uint64_t count, uint64_t* keys_out, void* rows_out,
                      double* m_out, double* v_out, psg_stream stream) {
-  return export_rows(t, first, count, keys_out, rows_out, m_out, v_out, stream);
+  const char* name = "psg_table_export";
+  PSG_TRY(require_table(name, t));
+  PSG_REQUIRE((m_out != nullptr) == (v_out != nullptr), PSG_ERR_INVALID, "%s: m_out and v_out come as a pair, %s is null",
+              name, m_out ? "v_out" : "m_out");
+  PSG_REQUIRE(!m_out || t->adam, PSG_ERR_INVALID, "%s: moments of a table without Adam state", name);
+  PSG_REQUIRE(first <= t->size && count <= t->size - first, PSG_ERR_INVALID,
+              "%s: rows [%llu, %llu + %llu) of a table of %llu", name, (unsigned long long)first,
+              (unsigned long long)first, (unsigned long long)count, (unsigned long long)t->size);
+  if (count == 0) return PSG_OK;
+  PSG_REQUIRE(rows_out, PSG_ERR_INVALID, "%s: null rows_out", name);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t row_bytes = (uint64_t)t->width * t->esize;
+  // keys and rows are in key order in the table: two copies inside HBM
+  if (keys_out)
+    PSG_HIP(hipMemcpyAsync(keys_out, t->keys + first, count * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  PSG_HIP(hipMemcpyAsync(rows_out, (const char*)t->rows + first * row_bytes, count * row_bytes,
+                         hipMemcpyDeviceToDevice, st));
+  if (m_out) PSG_TRY(move_moments<false>(t, nullptr, first, m_out, v_out, count, st));
+  return PSG_OK;
 }
 
+// ---- lookup and erase: the calls that never insert ---------------------------------
 int psg_table_lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* found, uint64_t n, psg_stream stream) {
-  return lookup(t, keys, out, found, n, stream);
+  const char* name = "psg_table_lookup";
+  PSG_TRY(require_table(name, t));
+  if (n == 0) return PSG_OK;
+  PSG_TRY(require_keys(name, keys));
+  PSG_REQUIRE(out || found, PSG_ERR_INVALID, "%s: out and found are both null", name);
+  PSG_TRY(require_count(name, n));
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(gate_begin(t, n, st));
+  PSG_TRY(launch_resolve(t, keys, n, t->gate, false, st));
+  // presence alone (out null) has no unit: it is launched as one 16-B unit a row
+  const uint32_t row_bytes = out ? t->width * (uint32_t)t->esize : 16;
+  PSG_TRY(for_raw_unit(out ? request_unit_bytes(t, PSG_PULL, nullptr, out) : 16, [&](auto u) {
+    return launch_read<decltype(u)>(t, out, found, n, row_bytes / (uint32_t)sizeof(u), st);
+  }));
+  // the one synchronisation: keys no longer read, the reply in memory, the flags on the host
+  PSG_TRY(gate_end(t, st));
+  return require_in_range(t);
 }
 
+// insert_missing backwards: the slots the list names are marked dead, the
+// ordered compaction over the S slots gives the survivors' old slots, and keys,
+// rows and moment rows are gathered into new arrays that replace the old ones
+// after one synchronisation.
 int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* erased_host, psg_stream stream) {
-  return erase(t, keys, n, erased_host, stream);
+  const char* name = "psg_table_erase";
+  PSG_TRY(require_table(name, t));
+  if (erased_host) *erased_host = 0;
+  if (n == 0) return PSG_OK;
+  PSG_TRY(require_keys(name, keys));
+  PSG_TRY(require_count(name, n));
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(resolve_first(t, keys, n, false, st));
+  PSG_TRY(require_in_range(t));
+  const uint64_t S = t->size;
+  if (S == 0) return PSG_OK;
+  const uint64_t ntiles = compact_tiles(S);
+  DevBuf dead, counts, from;
+  PSG_HIP(hipMalloc(&dead.p, S));
+  PSG_HIP(hipMalloc(&counts.p, (ntiles + 1) * sizeof(uint32_t)));
+  PSG_HIP(hipMemsetAsync(dead.p, 0, S, st));
+  k_mark_dead<<<grid_per_lane(n), kBlock, 0, st>>>(t->slots, n, (uint8_t*)dead.p);
+  const Alive alive = {(const uint8_t*)dead.p};
+  compact_count(S, (uint32_t*)counts.p, alive, st);
+  PSG_HIP(hipGetLastError());
+  uint64_t m = 0;  // the survivors
+  PSG_TRY(read_count((const uint32_t*)counts.p + ntiles, &m, st));
+  PSG_REQUIRE(m <= S, PSG_ERR_HIP, "%s: %llu survivors of %llu rows", name, (unsigned long long)m, (unsigned long long)S);
+  if (m == S) return PSG_OK;  // no key of the list is present
+  DevBuf K2, R2, M2;
+  uint64_t cap = 0;
+  if (m) {
+    cap = std::max<uint64_t>(m, 1024);
+    const uint64_t row_bytes = (uint64_t)t->width * t->esize;
+    PSG_HIP(hipMalloc(&from.p, m * sizeof(uint32_t)));
+    PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
+    PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
+    if (t->adam) PSG_HIP(hipMalloc(&M2.p, cap * mom_row_bytes(t)));
+    compact_emit(S, (const uint32_t*)counts.p, alive, EmitSurvivor{t->keys, (uint64_t*)K2.p, (uint32_t*)from.p}, st);
+    PSG_HIP(hipGetLastError());
+    PSG_TRY(move_rows(t, true, t->rows, R2.p, (const uint32_t*)from.p, m, st));
+    if (t->adam) PSG_TRY(launch_move<u32x4>(true, t->mom, M2.p, (const uint32_t*)from.p, m, t->width, st));
+    PSG_HIP(hipStreamSynchronize(st));
+  }
+  // a table whose last key went keeps no arrays
+  publish_arrays(t, K2, R2, M2, m, cap);
+  if (erased_host) *erased_host = S - m;
+  return PSG_OK;
 }
 
+// ---- the pooled calls ---------------------------------------------------------------
 int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* offsets, void* out, uint64_t n,
                             uint64_t nb, psg_stream stream) {
   return lookup_pooled("psg_table_lookup_pooled", t, keys, offsets, nullptr, PSG_POOL_SUM, out, n, nb, stream);
@@ -2425,12 +2342,92 @@ int psg_table_update_pooled_weighted(psg_table* t, const uint64_t* keys, const u
                        stream, nullptr);
 }
 
-int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys_host, const uint64_t* ns_host,
-                                   const uint64_t* const* offsets_host, const uint64_t* nbs_host,
-                                   const float* const* grads_host, float lr, int iteration, psg_stream stream,
-                                   int* path_host) {
-  return update_pooled_merged(t, k, keys_host, ns_host, offsets_host, nbs_host, grads_host, lr, iteration, stream,
-                              path_host);
+// ---- the round of pooled and plain frames ------------------------------------------
+// psg_table_update_merged's sorted path with update_pooled's payload: the k key
+// lists one behind the other in the sort's key buffer and, in its payload
+// buffer, every occurrence's gradient row in the frames' gradient arrays laid
+// end to end (k_row_index for a plain frame, k_bag_of for a pooled one, each
+// from its frame's first row).  A round of plain frames is
+// psg_table_update_merged's, one pooled frame is update_pooled's.
+int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* keys, const uint64_t* ns,
+                                   const uint64_t* const* offsets, const uint64_t* nbs, const float* const* grads,
+                                   float lr, int iteration, psg_stream stream, int* path_host) {
+  const char* name = "psg_table_update_pooled_merged";
+  PSG_TRY(require_table(name, t));
+  PSG_TRY(require_frame_count(name, k));
+  PSG_TRY(require_iteration(name, iteration));
+  PSG_REQUIRE(keys && ns && offsets && nbs && grads, PSG_ERR_INVALID, "%s: null keys, ns, offsets, nbs or grads array",
+              name);
+  bool pooled = false;
+  for (int j = 0; j < k; ++j) {
+    PSG_REQUIRE(keys[j] || ns[j] == 0, PSG_ERR_INVALID, "%s: null keys of frame %d", name, j);
+    if (offsets[j]) {
+      pooled = true;
+      PSG_REQUIRE(grads[j] || nbs[j] == 0, PSG_ERR_INVALID, "%s: null grads of pooled frame %d", name, j);
+      PSG_REQUIRE(nbs[j] > 0 || ns[j] == 0, PSG_ERR_INVALID, "%s: %llu keys of frame %d and no bag to hold them", name,
+                  (unsigned long long)ns[j], j);
+    } else {
+      PSG_REQUIRE(grads[j] || ns[j] == 0, PSG_ERR_INVALID, "%s: null grads of frame %d", name, j);
+    }
+  }
+  Frames f = round_frames(k);  // off: the first gradient row of each frame
+  decltype(f.off) koff;         // the first key of each frame in the concatenation
+  uint64_t N = 0, G = 0;
+  for (int j = 0; j < k; ++j) {
+    const uint64_t g = offsets[j] ? nbs[j] : ns[j];
+    PSG_TRY(require_round_count(name, N, ns[j]));
+    PSG_TRY(require_round_count(name, G, g, "gradient rows"));
+    koff[j] = (uint32_t)N;
+    f.off[j] = (uint32_t)G;
+    N += ns[j];
+    G += g;
+  }
+  PSG_TRY(require_f32(name, t));
+  if (path_host) *path_host = 0;
+  if (!pooled) return psg_table_update_merged(t, PSG_PUSH, k, keys, ns, grads, nullptr, lr, iteration, stream, path_host);
+  if (k == 1)
+    return update_pooled(name, t, keys[0], offsets[0], nullptr, PSG_POOL_SUM, grads[0], ns[0], nbs[0], lr, iteration,
+                         stream, path_host);
+  if (N == 0 && G == 0) return PSG_OK;  // no key and no bag: nothing to check either
+  hipStream_t st = (hipStream_t)stream;
+  // the front half: every offsets array checked before anything else reads it,
+  // every key against the range; one synchronisation, nothing written yet
+  AnyScratch a = {};
+  if (N) {
+    PSG_TRY(ensure_slots(t, N));  // ahead of resolve_first's own: the slots grow before the sort's scratch, as ever
+    PSG_TRY(any_scratch(t, N, &a));
+  }
+  PSG_TRY(resolve_first(t, a.k0, N, true, st, [&] {
+    for (int j = 0; j < k; ++j) {
+      if (offsets[j] && nbs[j]) PSG_TRY(launch_offsets_check(offsets[j], ns[j], nbs[j], t->flags, st));
+      PSG_TRY(copy_keys(a, koff[j], keys[j], ns[j], st));
+    }
+    return (int)PSG_OK;
+  }));
+  PSG_REQUIRE(!t->flags_host[R_OFFSETS], PSG_ERR_INVALID,
+              "%s: the offsets of a pooled frame do not start at 0, ascend and end at its ns", name);
+  PSG_TRY(require_in_range(t));
+  if (N == 0) return PSG_OK;  // every frame is empty: no gradient row is read
+  // the payload, and each frame's array moved back by its first row; 16-B units
+  // under optimize_vec's condition on every array that is read
+  bool vec = t->width % 4 == 0;
+  for (int j = 0; j < k; ++j) {
+    if (ns[j] == 0) continue;
+    if (offsets[j])
+      k_bag_of<<<grid_per_lane(nbs[j]), kBlock, 0, st>>>(offsets[j], nbs[j], f.off[j], a.p0 + koff[j]);
+    else
+      k_row_index<<<grid_per_lane(ns[j]), kBlock, 0, st>>>(a.p0 + koff[j], ns[j], f.off[j]);
+    PSG_HIP(hipGetLastError());
+    vec = vec && aligned16(grads[j]);
+    f.vals[j] = moved_back(t, (const void*)grads[j], f.off[j]);
+  }
+  AnyPlan plan;
+  PSG_TRY(plan_scratch(t, a, N, &plan, st, true));
+  PSG_TRY(pooled_step(t, vec, &plan, nullptr, nullptr, &f, {}, N, lr, iteration, st));
+  // complete on return: keys, offsets and grads no longer read
+  PSG_HIP(hipStreamSynchronize(st));
+  if (path_host) *path_host = PSG_MERGED_SORTED;
+  return PSG_OK;
 }
 
 int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host) {
