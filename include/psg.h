@@ -42,6 +42,9 @@
  *                    the bags of a routed list cut into the servers' shares, and
  *                    the servers' pooled rows added in rank order (no pooling in
  *                    the reference)
+ *   psg_pool_reduce_mean / psg_pool_scale_mean
+ *                    a mean over a sharded bag: the servers' sums divided once by
+ *                    the bag's length, and its gradient rows divided once
  *   psg_comm_*       the ZMQ data path of Van::Send / ZMQVan::SendMsg / ReceiveMsg
  *                    (src/internal/Van.cpp:170-179, src/internal/ZMQVan.cpp:147-248)
  *                    for the BSP case: Push = reduce-scatter + accumulate,
@@ -989,6 +992,54 @@ int psg_route_bags(const uint64_t* offsets, uint64_t nb, const uint32_t* perm, u
  * count == 0 is a no-op. */
 int psg_pool_reduce(void* out, const void* const* partials_host, int k, uint64_t count, int dtype,
                     psg_stream stream);
+/* Weighted and mean bags across servers: the other two poolings of
+ * psg_table_lookup_pooled_weighted / _update_pooled_weighted on a sharded table.
+ * WEIGHTS (PSG_POOL_SUM).  The n weights are routed like the keys (psg_rows_gather
+ * with perm and 4-B rows; the caller's own array on an identity route); server s
+ * gets weights[key_pos[s] .. key_pos[s+1]) and calls the weighted one-table call
+ * on its stretch with so[s].  Forward: the partials fold with psg_pool_reduce, as
+ * above.  Backward: keys, rows, moments and sizes over all servers end, bit for
+ * bit, as one whole-range table after psg_table_update_pooled_weighted(weights,
+ * PSG_POOL_SUM) on the whole list.
+ * MEAN.  No server sees a bag's whole length: so[s] gives only its share's.
+ * Forward: the servers answer plain SUM partials P_s and, per element i of bag b,
+ *   acc = (acc_t)+0
+ *   for s in rank order:  acc = acc + (acc_t)P_s[i]           -- one add each
+ *   out[i] = (dtype)(acc / (acc_t)L_b)    L_b = offsets[b+1] - offsets[b]
+ * with the CALLER's offsets: ONE correctly rounded division in acc_t (L_b read as
+ * 32 bits, converted round-to-nearest; no reciprocal), halves rounded once, at
+ * the end.  An empty bag stores +0 and divides nothing.  This is NOT the one-table
+ * arrival-order mean when a bag spans servers (the deviation of the fold above);
+ * with ONE partial from psg_table_lookup_pooled it is the one-table mean bit for
+ * bit for F32 and F64 (halves: the partial was rounded once already).
+ * Backward: E[i] = grads[bag(i)] / (float)L_bag(i) is one value for every id of a
+ * bag, so the nb gradient rows are divided ONCE,
+ *   dst[b*width + c] = grads[b*width + c] / (float)L_b        -- one f32 division
+ * (an empty bag: a row of +0, its grads row is not read), and every server runs
+ * psg_table_update_pooled on dst: bit for bit one whole-range table after
+ * psg_table_update_pooled_weighted(NULL, PSG_POOL_MEAN, grads).
+ *
+ * psg_pool_reduce_mean: the forward fold over nb * width elements of `dtype`;
+ * partials_host and k as psg_pool_reduce.  offsets: nb + 1 device words that
+ * psg_route_bags has accepted; they are not checked again.  16-B vectors only
+ * when a vector cannot straddle two bags: width * sizeof(T) is a multiple of 16
+ * and out and every partial are 16-B aligned; else one element per lane.  One
+ * writer per element, no atomics; (k + 1) * sizeof(T) bytes an element and 16 B
+ * a bag.  Stream-ordered.  Refused before any device call, in this order, with
+ * PSG_ERR_INVALID: k outside [1, PSG_ROUTE_MAX_SERVERS]; an unknown dtype; width
+ * outside [1, 4096]; with nb > 0 a null out, partials_host, offsets or partial;
+ * a pointer not aligned to its element (offsets: 8 B); out overlapping a
+ * partial.  Then PSG_ERR_RANGE: nb above 2^32 - 2.  nb == 0 is a no-op.
+ * psg_pool_scale_mean: the backward division, F32 only; dst and grads hold nb *
+ * width floats and must not overlap; vectors under the same rule; 8 B a float
+ * and 16 B a bag.  Refused in the same order: width; with nb > 0 a null dst,
+ * grads or offsets; misalignment; dst overlapping grads (all PSG_ERR_INVALID);
+ * then nb (PSG_ERR_RANGE).  nb == 0 is a no-op. */
+int psg_pool_reduce_mean(void* out, const void* const* partials_host, int k,
+                         const uint64_t* offsets, uint64_t nb, uint32_t width, int dtype,
+                         psg_stream stream);
+int psg_pool_scale_mean(float* dst, const float* grads, const uint64_t* offsets, uint64_t nb,
+                        uint32_t width, psg_stream stream);
 
 /* One pull reply (KVPairs from one server, KVApp.h:631-637). */
 typedef struct psg_segment {

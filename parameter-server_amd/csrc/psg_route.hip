@@ -37,6 +37,14 @@
 //                     list was left in place; writes nothing it was refused
 //   k_pool_reduce     one lane per 16-B vector (or element): k loads, k adds
 //                     from +0 in the accumulator's type, one store; no atomics
+// A mean over a sharded bag (no server sees a bag's whole length):
+//   psg_pool_reduce_mean  the fold of the servers' SUM partials, divided once by
+//                         the bag's length from the caller's offsets
+//   psg_pool_scale_mean   the bags' gradient rows divided once, into the pooled
+//                         frame every server then takes as a plain sum's
+//   k_pool_reduce_mean, k_pool_scale_mean   one lane per 16-B vector when a row
+//                     is whole vectors (no vector straddles two bags), else per
+//                     element; the two offsets words of the bag beside the loads
 #include <algorithm>
 #include <map>
 
@@ -331,6 +339,112 @@ __global__ __launch_bounds__(256) void k_pool_reduce(typename PoolAcc<DT, VEC>::
   }
 }
 
+// ---- a mean over a sharded bag --------------------------------------------------
+// A lane's grid-strided walk over nb rows of upr units: unit i is column c of
+// row b.  The first unit of a lane lies below 2^19 (the grid's cap), so the one
+// division is a 32-bit one; a step of the whole grid is (dr, dc), cut on the host.
+struct BagWalk {
+  uint64_t b;
+  uint32_t c, upr, dc;
+  uint64_t dr;
+  __device__ __forceinline__ BagWalk(uint32_t i0, uint32_t units_per_row, uint64_t step_rows, uint32_t step_cols)
+      : b(i0 / units_per_row), c(i0 - (i0 / units_per_row) * units_per_row), upr(units_per_row), dc(step_cols),
+        dr(step_rows) {}
+  __device__ __forceinline__ void next() {
+    b += dr;
+    c += dc;
+    if (c >= upr) {
+      c -= upr;
+      ++b;
+    }
+  }
+};
+
+// out unit i = round(fold(i) / L_b), fold as k_pool_reduce's, b the bag (row) of
+// unit i, L_b = offsets[b+1] - offsets[b] read as 32 bits: the mean of a bag
+// whose ids lie on several servers, from their SUM partials.  One correctly
+// rounded division in the accumulator's type (PoolAcc::over, as k_rows_pool); an
+// empty bag stores +0 and divides nothing.  A unit lies inside one row (VEC only
+// when a row is whole vectors), so a lane needs one length.  The two offsets
+// words are loaded with the partials, ahead of the adds.  (k + 1) * sizeof(U)
+// bytes a unit and 16 B a bag, which the lanes of a row share.
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void k_pool_reduce_mean(typename PoolAcc<DT, VEC>::U* __restrict__ out, Partials ps,
+                                                          int k, const uint64_t* __restrict__ offsets, uint64_t units,
+                                                          uint32_t upr, uint64_t dr, uint32_t dc) {
+  typedef PoolAcc<DT, VEC> P;
+  typedef typename P::U U;
+  const uint32_t i0 = blockIdx.x * kBlock + threadIdx.x;
+  BagWalk w(i0, upr, dr, dc);
+  for (uint64_t i = i0; i < units; i += (uint64_t)gridDim.x * kBlock, w.next()) {
+    const uint64_t o0 = offsets[w.b], o1 = offsets[w.b + 1];
+    typename P::A acc{};
+    int s = 0;
+    for (; s + 4 <= k; s += 4) {
+      const U v0 = ((const U*)ps.p[s])[i], v1 = ((const U*)ps.p[s + 1])[i];
+      const U v2 = ((const U*)ps.p[s + 2])[i], v3 = ((const U*)ps.p[s + 3])[i];
+      acc = P::add(acc, v0);
+      acc = P::add(acc, v1);
+      acc = P::add(acc, v2);
+      acc = P::add(acc, v3);
+    }
+    for (; s < k; ++s) acc = P::add(acc, ((const U*)ps.p[s])[i]);
+    const uint32_t len = (uint32_t)(o1 - o0);
+    if (len) acc = P::over(acc, len);
+    else acc = typename P::A{};
+    out[i] = P::round(acc);
+  }
+}
+
+// dst unit i = grads unit i / (float)L_b: the gradient rows of mean bags, divided
+// once for every server (k_pool_reduce_mean's walk and lengths).  An empty bag's
+// row is +0 and its gradient row is not read.  8 B a float and 16 B a bag.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_pool_scale_mean(typename PoolAcc<PSG_F32, VEC>::U* __restrict__ dst,
+                                                         const typename PoolAcc<PSG_F32, VEC>::U* __restrict__ grads,
+                                                         const uint64_t* __restrict__ offsets, uint64_t units,
+                                                         uint32_t upr, uint64_t dr, uint32_t dc) {
+  typedef PoolAcc<PSG_F32, VEC> P;
+  const uint32_t i0 = blockIdx.x * kBlock + threadIdx.x;
+  BagWalk w(i0, upr, dr, dc);
+  for (uint64_t i = i0; i < units; i += (uint64_t)gridDim.x * kBlock, w.next()) {
+    const uint32_t len = (uint32_t)(offsets[w.b + 1] - offsets[w.b]);
+    typename P::A acc{};
+    if (len) acc = P::over(P::widen(grads[i]), len);
+    dst[i] = P::round(acc);
+  }
+}
+
+// the grid of a walk over nb rows of upr units, and its step cut into (dr, dc)
+struct BagGrid {
+  uint64_t units, dr;
+  uint32_t upr, dc;
+  unsigned blocks;
+  BagGrid(uint64_t nb, uint32_t units_per_row) : units(nb * units_per_row), upr(units_per_row) {
+    blocks = (unsigned)std::min<uint64_t>((units + kBlock - 1) / kBlock, (uint64_t)max_stream_blocks());
+    const uint64_t step = (uint64_t)blocks * kBlock;
+    dr = step / upr;
+    dc = (uint32_t)(step - dr * upr);
+  }
+};
+
+template <int DT>
+int launch_pool_reduce_mean(void* out, const Partials& ps, int k, const uint64_t* offsets, uint64_t nb, uint32_t width,
+                            bool vec, hipStream_t st) {
+  const BagGrid g(nb, vec ? width / Elem<DT>::kVec : width);
+  if (vec)
+    k_pool_reduce_mean<DT, true><<<g.blocks, kBlock, 0, st>>>((typename PoolAcc<DT, true>::U*)out, ps, k, offsets,
+                                                              g.units, g.upr, g.dr, g.dc);
+  else
+    k_pool_reduce_mean<DT, false><<<g.blocks, kBlock, 0, st>>>((typename PoolAcc<DT, false>::U*)out, ps, k, offsets,
+                                                               g.units, g.upr, g.dr, g.dc);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+// [p, p + bytes) and [q, q + bytes) share no byte
+inline bool apart(uintptr_t p, uintptr_t q, unsigned __int128 bytes) { return p >= q ? p - q >= bytes : q - p >= bytes; }
+
 template <int DT>
 int launch_pool_reduce(void* out, const Partials& ps, int k, uint64_t count, bool vec, hipStream_t st) {
   const uint64_t units = vec ? count / Elem<DT>::kVec : count;
@@ -483,6 +597,73 @@ int psg_pool_reduce(void* out, const void* const* partials_host, int k, uint64_t
     case PSG_F16: return launch_pool_reduce<PSG_F16>(out, ps, k, count, vec, st);
     default: return launch_pool_reduce<PSG_BF16>(out, ps, k, count, vec, st);
   }
+}
+
+int psg_pool_reduce_mean(void* out, const void* const* partials_host, int k, const uint64_t* offsets, uint64_t nb,
+                         uint32_t width, int dtype, psg_stream stream) {
+  PSG_REQUIRE(k > 0 && k <= kMaxServers, PSG_ERR_INVALID, "psg_pool_reduce_mean: %d partials outside [1, %d]", k,
+              kMaxServers);
+  const uint64_t es = (uint64_t)dtype_size(dtype);
+  PSG_REQUIRE(es, PSG_ERR_INVALID, "psg_pool_reduce_mean: unknown dtype %d", dtype);
+  PSG_REQUIRE(width >= 1 && width <= 4096, PSG_ERR_INVALID, "psg_pool_reduce_mean: width %u outside [1, 4096]", width);
+  Partials ps;
+  for (int s = 0; s < kMaxServers; ++s) ps.p[s] = nullptr;
+  const uintptr_t o = reinterpret_cast<uintptr_t>(out);
+  uintptr_t a = o;
+  if (nb) {
+    PSG_REQUIRE(out && partials_host, PSG_ERR_INVALID, "psg_pool_reduce_mean: null out or partials");
+    PSG_REQUIRE(offsets, PSG_ERR_INVALID, "psg_pool_reduce_mean: null offsets");
+    for (int s = 0; s < k; ++s) {
+      ps.p[s] = partials_host[s];
+      PSG_REQUIRE(ps.p[s], PSG_ERR_INVALID, "psg_pool_reduce_mean: partial %d is null", s);
+      a |= reinterpret_cast<uintptr_t>(ps.p[s]);
+    }
+    PSG_REQUIRE(a % es == 0, PSG_ERR_INVALID, "psg_pool_reduce_mean: a pointer is not aligned to its %llu-byte elements",
+                (unsigned long long)es);
+    PSG_REQUIRE(reinterpret_cast<uintptr_t>(offsets) % 8 == 0, PSG_ERR_INVALID,
+                "psg_pool_reduce_mean: offsets are not aligned to 8 bytes");
+    const unsigned __int128 bytes = (unsigned __int128)nb * width * es;
+    for (int s = 0; s < k; ++s)
+      PSG_REQUIRE(apart(reinterpret_cast<uintptr_t>(ps.p[s]), o, bytes), PSG_ERR_INVALID,
+                  "psg_pool_reduce_mean: out overlaps partial %d", s);
+  }
+  PSG_REQUIRE(nb <= kMaxRouted, PSG_ERR_RANGE, "psg_pool_reduce_mean: %llu bags, more than 2^32-2", (unsigned long long)nb);
+  if (nb == 0) return PSG_OK;
+  // a 16-B vector per lane only when it cannot straddle two bags
+  const bool vec = (width * es) % 16 == 0 && a % 16 == 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (dtype) {
+    case PSG_F32: return launch_pool_reduce_mean<PSG_F32>(out, ps, k, offsets, nb, width, vec, st);
+    case PSG_F64: return launch_pool_reduce_mean<PSG_F64>(out, ps, k, offsets, nb, width, vec, st);
+    case PSG_F16: return launch_pool_reduce_mean<PSG_F16>(out, ps, k, offsets, nb, width, vec, st);
+    default: return launch_pool_reduce_mean<PSG_BF16>(out, ps, k, offsets, nb, width, vec, st);
+  }
+}
+
+int psg_pool_scale_mean(float* dst, const float* grads, const uint64_t* offsets, uint64_t nb, uint32_t width,
+                        psg_stream stream) {
+  PSG_REQUIRE(width >= 1 && width <= 4096, PSG_ERR_INVALID, "psg_pool_scale_mean: width %u outside [1, 4096]", width);
+  const uintptr_t d = reinterpret_cast<uintptr_t>(dst), g = reinterpret_cast<uintptr_t>(grads);
+  if (nb) {
+    PSG_REQUIRE(dst && grads, PSG_ERR_INVALID, "psg_pool_scale_mean: null dst or grads");
+    PSG_REQUIRE(offsets, PSG_ERR_INVALID, "psg_pool_scale_mean: null offsets");
+    PSG_REQUIRE((d | g) % 4 == 0, PSG_ERR_INVALID, "psg_pool_scale_mean: a pointer is not aligned to its 4-byte elements");
+    PSG_REQUIRE(reinterpret_cast<uintptr_t>(offsets) % 8 == 0, PSG_ERR_INVALID,
+                "psg_pool_scale_mean: offsets are not aligned to 8 bytes");
+    PSG_REQUIRE(apart(d, g, (unsigned __int128)nb * width * 4), PSG_ERR_INVALID, "psg_pool_scale_mean: dst overlaps grads");
+  }
+  PSG_REQUIRE(nb <= kMaxRouted, PSG_ERR_RANGE, "psg_pool_scale_mean: %llu bags, more than 2^32-2", (unsigned long long)nb);
+  if (nb == 0) return PSG_OK;
+  const bool vec = width % 4 == 0 && (d | g) % 16 == 0;
+  hipStream_t st = (hipStream_t)stream;
+  const BagGrid gr(nb, vec ? width / 4 : width);
+  if (vec)
+    k_pool_scale_mean<true><<<gr.blocks, kBlock, 0, st>>>((u32x4*)dst, (const u32x4*)grads, offsets, gr.units, gr.upr,
+                                                          gr.dr, gr.dc);
+  else
+    k_pool_scale_mean<false><<<gr.blocks, kBlock, 0, st>>>(dst, grads, offsets, gr.units, gr.upr, gr.dr, gr.dc);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
 }
 
 }  // extern "C"

@@ -87,6 +87,11 @@ struct Meta {
   // request: its LAST data frame holds the bag offsets of a pooled request
   // (KVPairs::offsets, uint64), behind the frames every other request carries
   bool bags = false;
+  // a pooled request with per-id weights (KVWorker::ZPullPooledWeighted /
+  // ZPushPooledWeighted): ONE more frame behind the offsets, the receiver's
+  // stretch of the routed weights (KVPairs::weights, f32 whatever Value is);
+  // bit 1 of the byte that carries bags
+  bool weighted = false;
   std::string body;
   std::vector<DataType> data_type;
   Control control;

@@ -55,6 +55,9 @@ struct KVPairs {
   // a pooled request (ZPullPooled / ZPushPooled): nb + 1 bag offsets into keys,
   // as psg_table_lookup_pooled takes them; empty on every other request
   SVector<uint64_t> offsets;
+  // a weighted pooled request (ZPullPooledWeighted / ZPushPooledWeighted): one
+  // f32 weight per key, whatever Value is; empty on every other request
+  SVector<float> weights;
 };
 
 /* meta of one request (KVApp.h:42-57) */
@@ -72,6 +75,7 @@ struct KVMeta {
 constexpr int kRowLookupPooled = 5;      // ZPullPooled
 constexpr int kRowUpdatePooled = 6;      // ZPushPooled
 constexpr int kRowUpdatePooledStep = 7;  // ZPushPooled(step): also ends worker 0's iteration
+constexpr int kRowLookupPooledMean = 8;  // ZPullPooledMean to ONE server: the one-table mean
 
 namespace detail {
 template <typename T>
@@ -474,6 +478,49 @@ class KVWorker : public SimpleApp {
                      bool step = false, const Callback& cb = nullptr, int priority = 0) {
     return SendPooled(keys, offsets, &grads, nullptr, step, true, cb, priority);
   }
+  /* ---- the other two poolings of a bag: per-id weights, and the mean ----------------
+   * The definitions are include/psg.h's ("Weighted and mean bags across servers").
+   * weights: n floats in HBM, one per position of keys (f32 whatever Value is).
+   * ZPullPooledWeighted / ZPushPooledWeighted: ZPullPooled / ZPushPooled with the
+   *   weights routed like the keys (psg_rows_gather on a permuted route, the
+   *   caller's own array on an identity route); every server that owns ids gets
+   *   its stretch of them as one more frame (Meta::weighted) and serves its share
+   *   with psg_table_lookup_pooled_weighted / _update_pooled_weighted(PSG_POOL_SUM).
+   * ZPullPooledMean: one server: cmd kRowLookupPooledMean with out offered, the
+   *   one-table mean bit for bit.  Several: the servers answer plain SUM partials
+   *   (cmd kRowLookupPooled) and, when the last reply is in, psg_pool_reduce_mean
+   *   folds them and divides once by the bag lengths of the CALLER's offsets
+   *   (also when one server owns every id).  No owners: out is +0.
+   * ZPushPooledMean / ZPushPooledMeanAll: psg_pool_scale_mean divides the nb
+   *   gradient rows once into a pooled frame, which goes the way ZPushPooled /
+   *   ZPushPooledAll send grads: a mean Push is a plain pooled Push to the
+   *   servers, sync-mode rounds included.
+   * CHECKs: what the unweighted calls CHECK; weights.size() == n and weights in
+   * HBM; the weighted and the mean Pushes need Value == float (the table's update
+   * is F32 only). */
+  int ZPullPooledWeighted(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<float>& weights,
+                          SVector<Value>* out, const Callback& cb = nullptr, int priority = 0) {
+    CHECK_NOTNULL(out);
+    return SendPooled(keys, offsets, nullptr, out, false, false, cb, priority, &weights);
+  }
+  int ZPushPooledWeighted(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<float>& weights,
+                          const SVector<Value>& grads, bool step = false, const Callback& cb = nullptr,
+                          int priority = 0) {
+    return SendPooled(keys, offsets, &grads, nullptr, step, false, cb, priority, &weights);
+  }
+  int ZPullPooledMean(const SVector<Key>& keys, const SVector<uint64_t>& offsets, SVector<Value>* out,
+                      const Callback& cb = nullptr, int priority = 0) {
+    CHECK_NOTNULL(out);
+    return SendPooled(keys, offsets, nullptr, out, false, false, cb, priority, nullptr, true);
+  }
+  int ZPushPooledMean(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>& grads,
+                      bool step = false, const Callback& cb = nullptr, int priority = 0) {
+    return SendPooled(keys, offsets, &grads, nullptr, step, false, cb, priority, nullptr, true);
+  }
+  int ZPushPooledMeanAll(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>& grads,
+                         bool step = false, const Callback& cb = nullptr, int priority = 0) {
+    return SendPooled(keys, offsets, &grads, nullptr, step, true, cb, priority, nullptr, true);
+  }
   /* Host-vector forms: the same routing done on the host (a stable counting
    * pass over the owners), the routed copies sent as host frames on its bounds,
    * the replies un-permuted on the host in the callback.  A correctness path,
@@ -580,9 +627,11 @@ class KVWorker : public SimpleApp {
   int SendAnyHost(const std::vector<Key>& keys, const std::vector<Value>* vals, std::vector<Value>* outs, int cmd,
                   const Callback& cb, int priority);
   /* ZPullPooled (grads == nullptr) and ZPushPooled / ZPushPooledAll (out ==
-   * nullptr; all: also the servers that own none of the ids are sent to) */
+   * nullptr; all: also the servers that own none of the ids are sent to);
+   * weights != nullptr: the Weighted calls; mean: the Mean calls */
   int SendPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>* grads,
-                 SVector<Value>* out, bool step, bool all, const Callback& cb, int priority);
+                 SVector<Value>* out, bool step, bool all, const Callback& cb, int priority,
+                 const SVector<float>* weights = nullptr, bool mean = false);
   void OnReceive(const Message& msg) override;
   void DefaultSlicer(Data& send, const std::vector<Range>& ranges, SlicedKVs* sliced);
   /* routed: the request went out on SendBounds — its keys are partitioned by
@@ -1168,6 +1217,12 @@ void KVServer<Value>::OnReceive(const Message& msg) {
   size_t n = msg.data.size();
   direct_out_ = SVector<Value>();
   direct_taken_ = false;
+  if (msg.meta.weighted) {
+    // a weighted pooled request: the weights ride behind the offsets
+    CHECK(msg.meta.bags) << "a weights frame belongs to a pooled request";
+    CHECK_GE(n, (size_t)4) << "a weighted pooled request carries keys, a values frame, its offsets and its weights";
+    data.weights = msg.data[--n];
+  }
   if (msg.meta.bags) {
     // a pooled request: the bag offsets ride behind the frames every other
     // request carries, which are parsed below as they always were
@@ -1616,9 +1671,13 @@ int KVWorker<Value>::SendAny(const SVector<Key>& keys, const SVector<Value>* val
 // owns ids — are held by the completion's captures until it has run.
 template <typename Value>
 int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t>& offsets, const SVector<Value>* grads,
-                                SVector<Value>* out, bool step, bool all, const Callback& cb, int priority) {
+                                SVector<Value>* out, bool step, bool all, const Callback& cb, int priority,
+                                const SVector<float>* weights, bool mean) {
   const bool pull = out != nullptr;
-  const char* who = pull ? "ZPullPooled" : all ? "ZPushPooledAll" : "ZPushPooled";
+  const char* who = weights ? (pull ? "ZPullPooledWeighted" : "ZPushPooledWeighted")
+                    : mean  ? (pull ? "ZPullPooledMean" : all ? "ZPushPooledMeanAll" : "ZPushPooledMean")
+                            : (pull ? "ZPullPooled" : all ? "ZPushPooledAll" : "ZPushPooled");
+  CHECK(!(weights && mean)) << "a mean bag takes no weights";
   CHECK(!(pull && all)) << "ZPullPooled asks the servers that own ids";
   CHECK(default_slicer_) << who << " routes by the servers' key ranges: it cannot be combined with a custom slicer";
   CHECK(keys.empty() || keys.on_device()) << who << ": keys live in HBM";
@@ -1631,6 +1690,12 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
   CHECK_EQ(nb ? vals.size() / nb * nb : (size_t)0, vals.size())
       << who << ": " << (pull ? "out" : "grads") << " holds a whole number of values per bag";
   const size_t count = vals.size();  // nb * k
+  if (weights) {
+    CHECK_EQ(weights->size(), n) << who << ": one weight per key";
+    CHECK(weights->empty() || weights->on_device()) << who << ": weights live in HBM";
+  }
+  if (!pull && (weights || mean))
+    CHECK((std::is_same<Value, float>::value)) << who << ": the table's update takes float gradients only";
   const std::vector<Range>& ranges = PostOffice::Get()->GetServerRanges();
   const size_t ns = ranges.size();
   const int dev = offsets.device();
@@ -1654,6 +1719,17 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
     if (identity) perm = SVector<uint32_t>();  // already partitioned: the caller's own keys
     else skeys = rkeys;
   }
+  // the weights as sent: routed like the keys (in memory when psg_route_bags returns)
+  SVector<float> sweights;
+  if (weights) {
+    sweights = *weights;
+    if (!perm.empty()) {
+      sweights = SVector<float>::OnDevice(n, dev);
+      stage::Scope t("worker.route.gather", 2 * n * sizeof(float));
+      device::Check(psg_rows_gather(sweights.data(), weights->data(), perm.data(), n, sizeof(float), st),
+                    "psg_rows_gather");
+    }
+  }
   // every server's share of every bag; returns once the offsets frame is in
   // memory (the servers read the frames on streams of their own)
   SVector<uint64_t> so = SVector<uint64_t>::OnDevice(ns * (nb + 1), dev);
@@ -1664,6 +1740,21 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
     CHECK(rc == PSG_OK) << who << ": " << psg_last_error() << " (nothing was sent)";
   }
   if (nb == 0) device::Check(psg_stream_sync(st), "psg_stream_sync");  // (no kernel ran: the route's writes)
+  // a mean Push: the gradient rows divided once, behind the offsets' check; the
+  // frame is then a plain pooled Push's
+  SVector<Value> scaled;
+  if (mean && !pull && count) {
+    scaled = SVector<Value>::OnDevice(count, dev);
+    if constexpr (std::is_same<Value, float>::value) {
+      stage::Scope t("worker.push.scale_mean", 2 * count * sizeof(Value));
+      device::Check(psg_pool_scale_mean(scaled.data(), grads->data(), offsets.data(), nb, (uint32_t)(count / nb), st),
+                    "psg_pool_scale_mean");
+      device::Check(psg_stream_sync(st), "psg_stream_sync");
+    }
+    grads = &scaled;
+  }
+  // one server serves a mean Pull whole (the one-table mean); several answer sums
+  const bool mean_whole = mean && pull && ns == 1;
   // the servers that are sent to: those that own ids, or (all) every one
   int owners = 0;
   for (size_t s = 0; s < ns; ++s) owners += all || pos[s + 1] != pos[s] ? 1 : 0;
@@ -1675,12 +1766,14 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
       if (pos[s + 1] != pos[s]) (*frames)[s] = ns == 1 ? *out : SVector<Value>::OnDevice(count, dev);
   const int ts = customer_->NewRequest(kServerGroup);
   if (!pull) {
-    AddCallback(ts, [skeys, perm, so, cb]() {
+    AddCallback(ts, [skeys, perm, so, sweights, scaled, cb]() {
       if (cb) cb();
     });
   } else {
     const SVector<Value> result = *out;  // shares the caller's buffer
-    AddCallback(ts, [this, ts, skeys, perm, so, frames, result, count, owners, cb]() mutable {
+    // (a mean over several servers reads the caller's offsets: kept alive here)
+    AddCallback(ts, [this, ts, skeys, perm, so, sweights, offs = offsets, mean, mean_whole, nb, frames, result, count, owners,
+                     cb]() mutable {
       std::vector<Reply> kvs;
       {
         std::lock_guard<std::mutex> lk(mu_);
@@ -1705,22 +1798,32 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
         if (!f.empty()) parts.push_back(f.data());
       if (owners == 0) {
         device::Check(psg_memset(result.data(), 0, count * sizeof(Value), s), "psg_memset");  // every bag is empty: +0
+      } else if (mean && !mean_whole) {
+        if (count)
+          device::Check(psg_pool_reduce_mean(result.data(), parts.data(), (int)parts.size(), offs.data(), nb,
+                                             (uint32_t)(count / nb), device::DType<Value>(), s),
+                        "psg_pool_reduce_mean");
       } else if (!(parts.size() == 1 && parts[0] == (const void*)result.data())) {
-        device::Check(psg_pool_reduce(result.data(), parts.data(), (int)parts.size(), count, device::DType<Value>(), s),
-                      "psg_pool_reduce");
+        if (mean_whole)  // the server's mean as it is (a fold from +0 would lose a -0)
+          device::Check(psg_memcpy(result.data(), parts[0], count * sizeof(Value), 2 /* D2D */, s), "psg_memcpy D2D");
+        else
+          device::Check(psg_pool_reduce(result.data(), parts.data(), (int)parts.size(), count, device::DType<Value>(), s),
+                        "psg_pool_reduce");
       }
       device::Check(psg_stream_sync(s), "psg_stream_sync");
       frames.reset();
       skeys = SVector<Key>();
       perm = SVector<uint32_t>();
       so = SVector<uint64_t>();
+      sweights = SVector<float>();
+      offs = SVector<uint64_t>();
       if (cb) cb();
     });
   }
   stage::Scope t_send(pull ? "worker.send.pull" : "worker.send.push");
   customer_->AddResponse(ts, (int)ns - owners);
   if (owners == 0) RunCallback(ts);
-  const int cmd = pull ? kRowLookupPooled : step ? kRowUpdatePooledStep : kRowUpdatePooled;
+  const int cmd = mean_whole ? kRowLookupPooledMean : pull ? kRowLookupPooled : step ? kRowUpdatePooledStep : kRowUpdatePooled;
   for (size_t s = 0; s < ns; ++s) {
     if (!all && pos[s + 1] == pos[s]) continue;
     Message msg;
@@ -1738,6 +1841,10 @@ int KVWorker<Value>::SendPooled(const SVector<Key>& keys, const SVector<uint64_t
     msg.AddData(skeys.Slice(pos[s], pos[s + 1]));
     msg.AddData(pull ? (direct ? (*frames)[s] : SVector<Value>()) : *grads);
     msg.AddData(so.Slice(s * (nb + 1), (s + 1) * (nb + 1)));
+    if (weights) {
+      msg.meta.weighted = true;
+      msg.AddData(sweights.Slice(pos[s], pos[s + 1]));
+    }
     PostOffice::Get()->van()->Send(msg);
   }
   return ts;

@@ -55,7 +55,16 @@ constexpr int kRowErase = 4;
 //                           KVServerRowSyncHandle holds them for its round
 //                           (psg_table_update_pooled_merged), KVServerRowHandle
 //                           fails a CHECK that says so.
-// A PushPull with any of the three fails the handle's CHECK.
+// With per-id weights (KVPairs::weights, KVWorker::ZPullPooledWeighted /
+// ZPushPooledWeighted) cmd 5 is psg_table_lookup_pooled_weighted(weights,
+// PSG_POOL_SUM) and cmd 6 / 7 psg_table_update_pooled_weighted on the optimizer
+// handle; the sync handle refuses a weighted Push (a round's frames carry none).
+//   kRowLookupPooledMean (8), on a Pull:  KVWorker::ZPullPooledMean to ONE server:
+//                           psg_table_lookup_pooled_weighted(NULL, PSG_POOL_MEAN),
+//                           the whole bags' mean; weights with it fail a CHECK.
+//                           (Over several servers a mean is cmd 5 and the
+//                           worker's division; a mean Push is a plain cmd 6 / 7.)
+// A PushPull with any of these fails the handle's CHECK.
 
 namespace detail {
 
@@ -117,7 +126,8 @@ void ServeRows(const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<
 // ServeRows for a pooled request (KVPairs::offsets: nb + 1 bag offsets into the
 // keys): a Pull answers nb * width values, into the frame the worker offered
 // when there is one; a Push carries nb * width values.  call(stream, keys,
-// offsets, vals, out, nb) wraps psg_table_lookup_pooled / _update_pooled.
+// offsets, weights, vals, out, nb) wraps psg_table_lookup_pooled / _update_pooled
+// or their weighted forms; weights: the request's, in HBM, or null without.
 template <typename Value, typename Call>
 void ServeRowsPooled(const char* who, const KVMeta& req_meta, const KVPairs<Value>& req_data, KVServer<Value>* server,
                      size_t width, const char* scope, Call call) {
@@ -127,6 +137,8 @@ void ServeRowsPooled(const char* who, const KVMeta& req_meta, const KVPairs<Valu
   const int dev = PostOffice::Get()->device();
   if (req_meta.push)
     CHECK_EQ(nb * width, req_data.vals.size()) << who << ": a pooled Push carries width values per bag";
+  if (!req_data.weights.empty())
+    CHECK_EQ(req_data.weights.size(), req_data.keys.size()) << who << ": a weighted pooled request carries one weight per key";
   KVPairs<Value> res;
   SVector<Value> dout;
   bool direct = false;
@@ -134,6 +146,7 @@ void ServeRowsPooled(const char* who, const KVMeta& req_meta, const KVPairs<Valu
     psg_stream s = device::ThreadStream();
     SVector<Key> dkeys = ToDeviceAsync(req_data.keys, dev);
     SVector<uint64_t> doffs = ToDeviceAsync(req_data.offsets, dev);
+    SVector<float> dweights = ToDeviceAsync(req_data.weights, dev);
     SVector<Value> dvals;
     if (req_meta.push) dvals = ToDeviceAsync(req_data.vals, dev);
     if (req_meta.pull) {
@@ -142,7 +155,7 @@ void ServeRowsPooled(const char* who, const KVMeta& req_meta, const KVPairs<Valu
       if (!direct) dout = SVector<Value>::OnDevice(nb * width, dev);
     }
     stage::Scope t(scope);
-    call(s, dkeys.data(), doffs.data(), dvals.data(), dout.data(), nb);
+    call(s, dkeys.data(), doffs.data(), dweights.empty() ? nullptr : dweights.data(), dvals.data(), dout.data(), nb);
   }
   if (req_meta.pull) {
     res.keys = req_data.keys;
@@ -151,30 +164,44 @@ void ServeRowsPooled(const char* who, const KVMeta& req_meta, const KVPairs<Valu
   server->Response(req_meta, res);
 }
 
-// The accumulate handle trains no row on a pooled gradient: called first, on
-// the host, before the request touches the device.
+// The accumulate handle trains no row on a pooled gradient, weighted or not:
+// called first, on the host, before the request touches the device.
 inline void RefusePooledUpdate(const char* who, const KVMeta& req_meta) {
   CHECK(!(req_meta.push && (req_meta.cmd == kRowUpdatePooled || req_meta.cmd == kRowUpdatePooledStep)))
       << who << ": a pooled update (cmd " << req_meta.cmd << ", KVWorker::ZPushPooled) is served by KVServerRowOptHandle "
       << "only; this handle does not merge pooled frames";
 }
 
-// A request with kRowLookup, kRowErase or kRowLookupPooled, served; false: it is
-// none of them (the pooled updates are the optimizer handle's own).
+// A request with kRowLookup, kRowErase, kRowLookupPooled or kRowLookupPooledMean,
+// served; false: it is none of them (the pooled updates are the optimizer
+// handle's own).
 template <typename Value>
 bool ServeRowLifecycle(const char* who, psg_table* table, const KVMeta& req_meta, const KVPairs<Value>& req_data,
                        KVServer<Value>* server, size_t width) {
   const int cmd = req_meta.cmd;
-  if (cmd != kRowLookup && cmd != kRowErase && !(cmd >= kRowLookupPooled && cmd <= kRowUpdatePooledStep)) return false;
+  if (cmd != kRowLookup && cmd != kRowErase && !(cmd >= kRowLookupPooled && cmd <= kRowLookupPooledMean)) return false;
   CHECK(!(req_meta.push && req_meta.pull))
       << who << ": a PushPull cannot carry cmd " << cmd
-      << " (kRowLookup and kRowLookupPooled go with a Pull, kRowErase and the pooled updates with a Push)";
+      << " (kRowLookup and the pooled lookups go with a Pull, kRowErase and the pooled updates with a Push)";
   const size_t n = req_data.keys.size();
-  if (req_meta.pull && cmd == kRowLookupPooled) {
+  if (req_meta.pull && cmd == kRowLookupPooled && req_data.weights.empty()) {
     ServeRowsPooled(who, req_meta, req_data, server, width, "server.handle.rows.lookup_pooled",
-                    [&](psg_stream s, const Key* keys, const uint64_t* offsets, const Value*, Value* out, size_t nb) {
+                    [&](psg_stream s, const Key* keys, const uint64_t* offsets, const float*, const Value*, Value* out,
+                        size_t nb) {
                       device::Check(psg_table_lookup_pooled(table, keys, offsets, out, n, nb, s),
                                     "psg_table_lookup_pooled");
+                    });
+    return true;
+  }
+  if (req_meta.pull && (cmd == kRowLookupPooled || cmd == kRowLookupPooledMean)) {
+    const bool mean = cmd == kRowLookupPooledMean;
+    CHECK(!(mean && !req_data.weights.empty())) << who << ": a mean lookup (cmd " << cmd << ") takes no weights";
+    ServeRowsPooled(who, req_meta, req_data, server, width, "server.handle.rows.lookup_pooled",
+                    [&](psg_stream s, const Key* keys, const uint64_t* offsets, const float* weights, const Value*,
+                        Value* out, size_t nb) {
+                      device::Check(psg_table_lookup_pooled_weighted(table, keys, offsets, weights,
+                                                                     mean ? PSG_POOL_MEAN : PSG_POOL_SUM, out, n, nb, s),
+                                    "psg_table_lookup_pooled_weighted");
                     });
     return true;
   }

@@ -26,7 +26,13 @@
 //                      one gradient row per bag (KVWorker::ZPushPooled), applied
 //                      at once with the current iteration
 //                      (psg_table_update_pooled); after a cmd 7 from worker 0
-//                      the iteration goes up by one, as after its cmd 1.
+//                      the iteration goes up by one, as after its cmd 1.  With
+//                      per-id weights (KVWorker::ZPushPooledWeighted):
+//                      psg_table_update_pooled_weighted(weights, PSG_POOL_SUM),
+//                      the step handled the same.  A mean Push
+//                      (ZPushPooledMean) arrives divided: a plain cmd 6 / 7.
+//   Pull, cmd 5 with weights, cmd 8:  the weighted and the mean lookup
+//                      (ps/row_handle.h).
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first request
 // (or by SaveModel / LoadModel, which write and read rows, moments and iteration);
@@ -88,11 +94,17 @@ struct KVServerRowOptHandle {
       // worker 0's kRowUpdatePooledStep ends an iteration, as its cmd 1 does
       const bool ends = req_meta.cmd == kRowUpdatePooledStep && req_meta.sender == PostOffice::WorkerRankToID(0);
       detail::ServeRowsPooled("KVServerRowOptHandle", req_meta, req_data, server, w, "server.handle.rows.update_pooled",
-                              [&](psg_stream s, const Key* keys, const uint64_t* offsets, const float* grads, float*,
-                                  size_t nb) {
-                                device::Check(psg_table_update_pooled(st.table, keys, offsets, grads, n, nb, st.lr,
-                                                                      st.iteration, s),
-                                              "psg_table_update_pooled");
+                              [&](psg_stream s, const Key* keys, const uint64_t* offsets, const float* weights,
+                                  const float* grads, float*, size_t nb) {
+                                if (weights)
+                                  device::Check(psg_table_update_pooled_weighted(st.table, keys, offsets, weights,
+                                                                                 PSG_POOL_SUM, grads, n, nb, st.lr,
+                                                                                 st.iteration, s),
+                                                "psg_table_update_pooled_weighted");
+                                else
+                                  device::Check(psg_table_update_pooled(st.table, keys, offsets, grads, n, nb, st.lr,
+                                                                        st.iteration, s),
+                                                "psg_table_update_pooled");
                               });
       if (ends) ++st.iteration;
       return;

@@ -42,6 +42,12 @@
 //                      (psg_table_handle_any): the updated row for every
 //                      occurrence, the bytes psg_table_update_merged's Pull leg
 //                      gives.  A round without one is exactly the call above.
+//                      A mean Push (KVWorker::ZPushPooledMeanAll) arrives divided
+//                      and is such a frame.  A WEIGHTED pooled Push fails a CHECK
+//                      before it is held: a round's frames carry no weights
+//                      (psg_table_update_pooled_merged has none).
+//   Pull, cmd 5 with weights, cmd 8:  the weighted and the mean lookup, at once
+//                      (ps/row_handle.h).
 //
 // The iteration goes up by one after a round is applied, if the round held
 // worker 0's Push with cmd == 1 or kRowUpdatePooledStep.  The reference counts when that Push arrives
@@ -120,6 +126,9 @@ struct KVServerRowSyncHandle {
     if (detail::ServeRowLifecycle("KVServerRowSyncHandle", st.table, req_meta, req_data, server, w)) return;
     const bool pooled = req_meta.push && (req_meta.cmd == kRowUpdatePooled || req_meta.cmd == kRowUpdatePooledStep);
     if (pooled) {
+      CHECK(req_data.weights.empty())
+          << "KVServerRowSyncHandle: a weighted pooled Push (cmd " << req_meta.cmd << ", KVWorker::ZPushPooledWeighted) "
+          << "cannot join a round: a round's frames carry no weights (psg_table_update_pooled_merged has none)";
       CHECK(!req_data.offsets.empty()) << "KVServerRowSyncHandle: cmd " << req_meta.cmd
                                        << " needs the bag offsets of a pooled request (KVWorker::ZPushPooledAll)";
       CHECK_EQ((req_data.offsets.size() - 1) * w, req_data.vals.size())

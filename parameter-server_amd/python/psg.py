@@ -56,6 +56,7 @@ EXPORTS = [
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
     "psg_table_lookup_pooled_weighted", "psg_table_update_pooled_weighted", "psg_table_update_pooled_merged",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
+    "psg_pool_reduce_mean", "psg_pool_scale_mean",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
     "psg_comm_init", "psg_comm_destroy", "psg_comm_rank", "psg_comm_push", "psg_comm_pull",
     "psg_comm_push_pull", "psg_comm_push_keyed", "psg_comm_pull_keyed",
@@ -183,6 +184,8 @@ def lib() -> C.CDLL:
             "psg_rows_scatter": ([vp, vp, vp, u64, u64, vp], i32),
             "psg_route_bags": ([vp, u64, vp, u64, i32, vp, vp, vp], i32),
             "psg_pool_reduce": ([vp, C.POINTER(vp), i32, u64, i32, vp], i32),
+            "psg_pool_reduce_mean": ([vp, C.POINTER(vp), i32, vp, u64, C.c_uint32, i32, vp], i32),
+            "psg_pool_scale_mean": ([vp, vp, vp, u64, C.c_uint32, vp], i32),
             "psg_comm_id_bytes": ([], i32), "psg_comm_get_id": ([vp], i32),
             "psg_comm_bucket_plan": ([u64, i32, vp, vp, i32, C.POINTER(i32)], i32),
             "psg_comm_sync": ([vp, vp, f64], i32), "psg_comm_abort": ([vp], i32),
@@ -755,6 +758,21 @@ def pool_reduce(out, partials, count: int, dtype: int, stream=None) -> None:
     k = len(partials)
     arr = (C.c_void_p * max(k, 1))(*[_ptr(p) for p in partials])
     _call("psg_pool_reduce", _ptr(out), arr, k, count, dtype, _s(stream))
+
+
+def pool_reduce_mean(out, partials, offsets, nb: int, width: int, dtype: int, stream=None) -> None:
+    """out[b] = the servers' SUM partials[s][b] added in list order from +0, then
+    divided once by bag b's length offsets[b + 1] - offsets[b]; an empty bag is +0
+    (psg_pool_reduce_mean); nb rows of `width` elements of `dtype`; stream-ordered."""
+    k = len(partials)
+    arr = (C.c_void_p * max(k, 1))(*[_ptr(p) for p in partials])
+    _call("psg_pool_reduce_mean", _ptr(out), arr, k, _ptr(offsets), nb, width, dtype, _s(stream))
+
+
+def pool_scale_mean(dst, grads, offsets, nb: int, width: int, stream=None) -> None:
+    """dst row b = grads row b / (float)(offsets[b + 1] - offsets[b]), +0 for an
+    empty bag (psg_pool_scale_mean); nb rows of `width` floats; stream-ordered."""
+    _call("psg_pool_scale_mean", _ptr(dst), _ptr(grads), _ptr(offsets), nb, width, _s(stream))
 
 
 def merge(segments, elem_size: int, dst, dst_count: int, stream=None) -> None:
