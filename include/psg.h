@@ -496,7 +496,8 @@ int psg_table_clear(psg_table* t, psg_stream stream);
  * keys: n device keys, strictly ascending (the KVPairs contract, KVApp.h:23);
  * vals / out: device arrays of n * width elements of the table's dtype.  Each
  * add is rounded to the dtype as psg_store_handle rounds it.  An absent key
- * is inserted with a zero row, on a Push and on a Pull (operator[]).  Keys out
+ * is inserted with a zero row or the table's initial row (psg_table_set_init),
+ * on a Push and on a Pull (operator[]).  Keys out
  * of order or repeated fail the request with PSG_ERR_INVALID, a key outside
  * the range with PSG_ERR_RANGE; every key is checked before the first write,
  * so a request that fails leaves the table bit for bit unchanged (such lists
@@ -511,9 +512,10 @@ int psg_table_handle(psg_table* t, int flags, const uint64_t* keys, const void* 
  * out + i*width, 1, stream) for i = 0 .. n-1.  Every occurrence of a key is
  * applied in arrival order and rounded on its own; a PushPull answers each
  * occurrence with the running row after it, a Pull answers every occurrence
- * with the row; an absent key is inserted once, with a zero row, however often
- * it is named.  A strictly ascending list is served exactly as psg_table_handle
- * serves it (the same kernels); any other list is sorted stably by key on the
+ * with the row; an absent key is inserted once, with a zero row or the table's
+ * initial row (psg_table_set_init), however often it is named.  A strictly
+ * ascending list is served exactly as psg_table_handle serves it (the same
+ * kernels); any other list is sorted stably by key on the
  * device and each row is walked over its occurrences by one writer.  Arguments
  * are checked as psg_table_handle checks them; a key outside the range fails
  * the request with PSG_ERR_RANGE before anything is written.  The caller's
@@ -549,8 +551,8 @@ int psg_table_set_adam(psg_table* t, double learning_rate, double beta1, double 
  * (PSG_ERR_UNSUPPORTED).  Keys, validation and return as psg_table_handle: keys
  * strictly ascending, every key checked before the first write, a rejected
  * request (PSG_ERR_INVALID / PSG_ERR_RANGE) leaves rows and moments bit for bit
- * unchanged; an absent key is inserted with a zero row and zero moments, then
- * updated.  n == 0 is a no-op. */
+ * unchanged; an absent key is inserted with a zero row or the table's initial
+ * row (psg_table_set_init) and zero moments, then updated.  n == 0 is a no-op. */
 int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float* grads,
                      float* out, uint64_t n, float lr, int iteration, psg_stream stream);
 /* psg_table_update for a key list in any order and with repeats: rows, moments
@@ -558,8 +560,9 @@ int psg_table_update(psg_table* t, int flags, const uint64_t* keys, const float*
  * psg_table_update(t, flags, keys + i, grads + i*width, out + i*width, 1, lr,
  * iteration, stream) for i = 0 .. n-1.  Every occurrence uses the request's one
  * `iteration` (c1 and c2 are evaluated once); the moments advance once per
- * occurrence; an absent key starts from a zero row and zero moments and is
- * inserted once.  Checks, the PSG_ERR_RANGE failure that writes nothing, the
+ * occurrence; an absent key starts from a zero row or the table's initial row
+ * (psg_table_set_init) and zero moments and is inserted once.  Checks, the
+ * PSG_ERR_RANGE failure that writes nothing, the
  * strictly ascending fast path and the return are those of
  * psg_table_handle_any and psg_table_update. */
 int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const float* grads,
@@ -582,7 +585,8 @@ int psg_table_update_any(psg_table* t, int flags, const uint64_t* keys, const fl
  * The sum starts from +0.0f and the first add is kept (0.0f + -0.0f is +0.0f).
  * This is what separates it from psg_table_update_any, which takes one step per
  * occurrence.  c1 and c2 are evaluated once on the host from `iteration`.  An
- * absent key is inserted once with a zero row and zero moments, then updated.
+ * absent key is inserted once with a zero row or the table's initial row
+ * (psg_table_set_init) and zero moments, then updated.
  * flags: PSG_PUSH or PSG_PUSH | PSG_PULL; outs_host may be NULL for PSG_PUSH.
  * F32 tables only (PSG_ERR_UNSUPPORTED).  Refused with PSG_ERR_INVALID before
  * any device call: a null table, k outside [1, 16], iteration < 0, a null array
@@ -610,6 +614,57 @@ int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host);
  * epsilon (zeros without Adam state).  Host only. */
 int psg_table_get_adam(psg_table* t, int* has_adam, double* params4);
 
+/* What a NEW row starts from.  The reference's store[key] value-initialises to
+ * zero (src/ps/KVApp.h:446-454), and so does a table by default; a model that
+ * multiplies two looked-up rows never leaves the origin from there, so a table
+ * can be told to start every row from a seeded uniform value instead.  The
+ * value is a pure function of (seed, key, column): it does not depend on the
+ * order of insertion, the slot, the request, the server or the row's width
+ * beyond the column, so a sharded table equals the whole-range one and a
+ * resumed run the uninterrupted one, bit for bit, as they do from zero rows.
+ * Element j of the initial row of key K under (seed, lo, hi):
+ *   x    = Philox4x32-10( counter = { (uint32)K, (uint32)(K >> 32), j / 4, 0 },
+ *                         key     = { (uint32)seed, (uint32)(seed >> 32) } ) [ j % 4 ]
+ *   u    = (float)(x >> 8) * 0x1p-24f                 -- exact, in [0, 1)
+ *   span = hi - lo                                    -- one f32 subtraction, on the host, once
+ *   v    = lo + u * span                              -- one f32 multiply, then one f32 add, NEVER fused
+ *   row(K)[j] = v in the table's dtype                -- F32 as is; F64 widened (exact);
+ *                                                        F16 / BF16 rounded to nearest even
+ * Philox is the standard one (Salmon et al., Random123): multipliers 0xD2511F53
+ * and 0xCD9E8D57, Weyl constants 0x9E3779B9 and 0xBB67AE85, ten rounds; counter
+ * 0 0 0 0 under key 0 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.  v lies in
+ * [lo, hi]: the add may round to hi itself.  Adam moments of a new row stay zero.
+ * kind: PSG_INIT_ZERO (the default, said aloud) or PSG_INIT_UNIFORM.  With
+ * PSG_INIT_UNIFORM set, every call that inserts an absent key stores its initial
+ * row where it stored a zero row, and the calls that never insert answer an
+ * absent id with it (psg_table_lookup, the pooled lookups): a lookup equals the
+ * Pull that would follow it, without the insert.  Set it before the first
+ * request: rows already present are left as they are.  psg_table_clear keeps
+ * the setting.  Any dtype, any width.  Refused with PSG_ERR_INVALID before any
+ * device call, in this order: a null table; an unknown kind; a second call on
+ * the table; lo or hi not finite; lo > hi; hi - lo not finite in f32.  lo == hi
+ * is allowed and gives constant rows.  Host only. */
+#define PSG_INIT_ZERO 0
+#define PSG_INIT_UNIFORM 1
+int psg_table_set_init(psg_table* t, int kind, uint64_t seed, float lo, float hi);
+/* What psg_table_set_init got: *kind (PSG_INIT_ZERO for a table it was never
+ * called on, with seed 0 and lo = hi = 0) and, where they are not NULL, *seed,
+ * *lo, *hi.  A null table or a null kind -> PSG_ERR_INVALID.  Host only. */
+int psg_table_get_init(psg_table* t, int* kind, uint64_t* seed, float* lo, float* hi);
+/* The generator on its own, no table involved: out[i*width + j] = element j of
+ * the initial row of keys[i] under (seed, lo, hi), as defined above, for i < n.
+ * keys: n device keys, any uint64, in any order and with repeats; out: n * width
+ * elements of `dtype` on the device.  This is what a worker uses to predict a
+ * row it has never pulled.  Rows of a multiple of 16 B into an `out` on 16 B are
+ * written as 16-B units, anything else element-wise; the bytes are the same.
+ * Refused before any device call, in this order, with PSG_ERR_INVALID: a bad
+ * dtype; width outside [1, 4096]; null out, then null keys (each with n > 0);
+ * out not on an element boundary; lo, hi as psg_table_set_init refuses them;
+ * then with PSG_ERR_RANGE n above 2^32 - 2.  n == 0 is a no-op.  Returns as
+ * psg_table_lookup: keys are no longer read, out is in memory. */
+int psg_init_rows(void* out, const uint64_t* keys, uint64_t n, int dtype, uint32_t width,
+                  uint64_t seed, float lo, float hi, psg_stream stream);
+
 /* Put rows (and Adam moments) into the table as they are: the reading half of
  * a saved model, lr::InitWeight with USE_OLD_MODEL (tests/src/LRServer.h:36-63:
  * `input >> weight[i]` sets a weight, it does not add to it).  For i < n,
@@ -633,7 +688,8 @@ int psg_table_get_adam(psg_table* t, int* has_adam, double* params4);
  * first write: out of order or repeated -> PSG_ERR_INVALID, a key outside the
  * range -> PSG_ERR_RANGE, and keys, rows, moments and size stay bit for bit
  * unchanged.  rows may be NULL (then m and v must be): the list's absent keys
- * are inserted with zero rows and zero moments and nothing else is written, so
+ * are inserted with zero rows or the table's initial rows (psg_table_set_init)
+ * and zero moments and nothing else is written, so
  * a model that arrives in chunks costs one merge instead of one per chunk.
  * Returns as psg_table_handle: keys, rows, m and v are no longer read.
  * n == 0 is a no-op. */
@@ -658,7 +714,9 @@ int psg_table_export(psg_table* t, uint64_t first, uint64_t count, uint64_t* key
  * occurrence i < n:
  *   key_i present:  out[i*width .. i*width + width) = the row AS BYTES (signed
  *                   zeros and NaN payloads as they are stored), found[i] = 1;
- *   otherwise:      the row is all zero bytes, found[i] = 0.
+ *   otherwise:      the row is all zero bytes or, on a table with an initializer,
+ *                   the table's initial row of key_i (psg_table_set_init: the
+ *                   bytes an insert would store), found[i] = 0.
  * out: n * width elements of the table's dtype on the device, or NULL
  * (presence only); found: n device bytes, or NULL.  The table is unchanged:
  * size, capacity, keys, rows and moments stay bit for bit and the device
@@ -676,7 +734,8 @@ int psg_table_lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* fou
  * any order and with repeats; absent keys are ignored.  *erased_host (may be
  * NULL) gets the number of rows removed.  The survivors keep their rows and
  * moments bit for bit, in key order; an erased key that is named again later
- * starts as any absent key does, from a zero row and zero moments.  Memory
+ * starts as any absent key does, from a zero row or the table's initial row
+ * (psg_table_set_init) and zero moments.  Memory
  * follows the rows: after a call that removed something capacity <=
  * max(2 * size, 1024), and a table whose last key went holds no arrays, like a
  * table created with capacity 0.  A call that removes nothing (n == 0, an
@@ -705,7 +764,10 @@ int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* er
  *   out[b*width + c] = (dtype)acc     -- halves: one round-to-nearest-even, at the end
  * An absent id adds nothing and is NOT inserted; an empty bag, or a bag of
  * absent ids, gives a row of +0 (and a bag of -0.0 rows too: the sum starts
- * from +0).  The table is unchanged as psg_table_lookup leaves it: size,
+ * from +0).  On a table with an initializer (psg_table_set_init) an absent id
+ * adds its initial row as a present one adds its row, and is still not
+ * inserted: the sum is the one the model sees once the update has inserted it.
+ * The table is unchanged as psg_table_lookup leaves it: size,
  * capacity, keys, rows, moments and the device pointers of psg_table_info;
  * nothing is allocated but request scratch.
  * Refused with PSG_ERR_INVALID before any device call, in this order: a null
@@ -732,7 +794,8 @@ int psg_table_lookup_pooled(psg_table* t, const uint64_t* keys, const uint64_t* 
  * summed from +0.0f in arrival order of its occurrences, one f32 add each, then
  * the optimizer steps ONCE (SGD, or Adam after psg_table_set_adam; LRServer.h:
  * 182-189, tests/src/Adam.h:28-34).  An absent id is inserted once with a zero
- * row and zero moments, then updated.  An empty bag's gradient row is not read.
+ * row or the table's initial row (psg_table_set_init) and zero moments, then
+ * updated.  An empty bag's gradient row is not read.
  * The reference has no pooling here either.  F32 tables only
  * (PSG_ERR_UNSUPPORTED).  Refused before any device call as the lookup refuses,
  * with grads in out's place, and iteration < 0 with PSG_ERR_INVALID.  The
@@ -762,13 +825,16 @@ int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* 
  *   out[b*width + c] = (dtype)acc     -- halves: one round-to-nearest-even, at the end
  * Two roundings per id and never a fused multiply-add: the library is built
  * with -ffp-contract=off.  An absent id adds nothing whatever its weight (a NaN
- * weight on an absent id does not reach the bag) and is NOT inserted.  weights
+ * weight on an absent id does not reach the bag) and is NOT inserted; on a table
+ * with an initializer (psg_table_set_init) it adds weights[p] times its initial
+ * row, the two roundings of a present id, and is still not inserted.  weights
  * == NULL with PSG_POOL_SUM IS psg_table_lookup_pooled: its path, its kernels,
  * its bits.
  * FORWARD, PSG_POOL_MEAN.  weights must be NULL.  acc is the unweighted sum,
  * then out[b*width + c] = (dtype)(acc / (acc_t)L_b) with L_b = offsets[b+1] -
- * offsets[b]: the bag's positions, present or not (an absent id is a zero row,
- * as everywhere in this table).  L_b is converted round-to-nearest and the
+ * offsets[b]: the bag's positions, present or not (an absent id is a zero row
+ * or the table's initial row, psg_table_set_init, as everywhere in this table).
+ * L_b is converted round-to-nearest and the
  * divide is ONE correctly rounded division, not a multiply by a reciprocal.  An
  * empty bag gives a row of +0 and divides nothing.
  * BACKWARD.  Rows, Adam moments, keys and size end, bit for bit, as after
@@ -822,8 +888,8 @@ int psg_table_update_pooled_weighted(psg_table* t, const uint64_t* keys, const u
  * grads_j[bag_j(i)*width + c] for a pooled one; no E_j is ever built.  Per id the
  * gradient rows of all its occurrences are summed from +0.0f in arrival order
  * (frame 0 .. k-1, then position), one f32 add each, then the optimizer steps
- * ONCE.  An absent id is inserted once with a zero row and zero moments, then
- * updated.  An empty bag's gradient row is never read.  Push only: there is no
+ * ONCE.  An absent id is inserted once with a zero row or the table's initial
+ * row (psg_table_set_init) and zero moments, then updated.  An empty bag's gradient row is never read.  Push only: there is no
  * reply.
  * Refused before any device call, in this order: PSG_ERR_INVALID for a null
  * table; k outside [1, 16]; iteration < 0; any of the five host arrays null;

@@ -112,6 +112,11 @@ struct psg_table {
   // psg_table_lookup's flag words on the device (kNFlags ints, on first use):
   // raised by its resolve and read by its walk, with no host in between
   int* gate;
+  // what a new row starts from (psg_table_set_init): PSG_INIT_ZERO until it is
+  // set, then the triple of PSG_INIT_UNIFORM; init_set: the one call was made
+  int init_kind, init_set;
+  uint64_t init_seed;
+  float init_lo, init_hi;
 };
 
 namespace psg {
@@ -730,6 +735,243 @@ __global__ __launch_bounds__(256) void k_rows_pool(const U* __restrict__ R, cons
             if (s0 != kAbsent) acc = ACC::add(acc, v);
           }
           s0 = s1, s1 = s2, v = vn;
+        }
+        if constexpr (POOL == kPoolMean) acc = ACC::over(acc, len);
+      }
+      out[b * upr + c] = ACC::round(acc);
+    }
+  }
+}
+
+// ---- the initial rows (psg_table_set_init / psg_init_rows) ------------------------
+// Element j of the initial row of key K (include/psg.h): word j % 4 of
+// Philox4x32-10 on the counter {K lo, K hi, j / 4, 0} under the key {seed lo,
+// seed hi}; its upper 24 bits as u in [0, 1); lo + u * span in f32, the multiply
+// and the add each rounded (the file is built with -ffp-contract=off); then the
+// table's dtype.  Nothing else enters, so a row is the same wherever and
+// whenever it is made: in the insert's fill, in a lookup that finds its key
+// absent, on another server, after a restart.
+// A block is ten rounds of two 32 x 32 -> 64 multiplies (20 v_mad_u64_u32).
+struct InitSpec {
+  uint32_t k0, k1;  // the seed's words
+  float lo, span;   // span = hi - lo, subtracted once on the host
+};
+
+__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                       uint32_t k1, uint32_t x[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c0 = n0, c1 = (uint32_t)p1, c2 = n2, c3 = (uint32_t)p0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
+}
+
+// block b of key's initial row: elements 4b .. 4b + 3 as f32
+__device__ __forceinline__ void init_block(uint64_t key, uint32_t b, const InitSpec& s, float v[4]) {
+  uint32_t x[4];
+  philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), b, 0u, s.k0, s.k1, x);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float u = (float)(x[e] >> 8) * 0x1p-24f;  // exact
+    const float prod = u * s.span;
+    v[e] = s.lo + prod;
+  }
+}
+
+// v[w] for a word index that is not a constant: selects, no indexed register file
+__device__ __forceinline__ float pick4(const float v[4], uint32_t w) {
+  return w == 0 ? v[0] : w == 1 ? v[1] : w == 2 ? v[2] : v[3];
+}
+
+// Unit c of key's initial row as the table stores it.  VEC: the 16-B unit (F32:
+// one block; F16 / BF16: blocks 2c and 2c + 1, rounded to nearest even; F64:
+// half of block c / 2, widened), else element c (its block, one word kept).
+template <int DT, bool VEC> struct InitUnit;
+template <int DT> struct InitUnit<DT, true> {
+  typedef u32x4 U;
+  __device__ static __forceinline__ U make(uint64_t key, uint32_t c, const InitSpec& s) {
+    float v[8];
+    if constexpr (DT == PSG_F32) {
+      init_block(key, c, s, v);
+      return __builtin_bit_cast(U, f32x4{v[0], v[1], v[2], v[3]});
+    } else if constexpr (DT == PSG_F64) {
+      init_block(key, c >> 1, s, v);
+      const bool up = (c & 1) != 0;
+      return __builtin_bit_cast(U, f64x2{(double)(up ? v[2] : v[0]), (double)(up ? v[3] : v[1])});
+    } else {
+      init_block(key, 2 * c, s, v);
+      init_block(key, 2 * c + 1, s, v + 4);
+      typename PoolVec<DT>::A a = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+      return __builtin_bit_cast(U, __builtin_convertvector(a, typename PoolVec<DT>::V));
+    }
+  }
+};
+template <int DT> struct InitUnit<DT, false> {
+  typedef typename Elem<DT>::T T;
+  typedef typename std::conditional<sizeof(T) == 8, uint64_t,
+                                    typename std::conditional<sizeof(T) == 4, uint32_t, uint16_t>::type>::type U;
+  __device__ static __forceinline__ U bits(float x) { return __builtin_bit_cast(U, (T)x); }
+  __device__ static __forceinline__ U make(uint64_t key, uint32_t c, const InitSpec& s) {
+    float v[4];
+    init_block(key, c >> 2, s, v);
+    return bits(pick4(v, c & 3));
+  }
+};
+
+// The initial rows of keys[j] for j < nrows: row j of dst, or row to[j] where
+// `to` is not null (insert_missing: miss and new_to).  VEC: a lane makes and
+// stores one 16-B unit.  Else a lane makes ONE block and stores its up to four
+// elements (the row's last block may be short); upr counts blocks, (width + 3) /
+// 4.  Consecutive lanes write consecutive memory either way; one writer per
+// element.  Per 16 B written: 20 wide multiplies (F32), 40 (halves), 10 (F64).
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void k_rows_init(typename InitUnit<DT, VEC>::U* __restrict__ dst,
+                                                   const uint64_t* __restrict__ keys, const uint32_t* __restrict__ to,
+                                                   uint64_t nrows, uint32_t width, uint32_t upr, uint32_t rpt,
+                                                   InitSpec spec) {
+  const uint64_t ntiles = (nrows + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t j0 = t * rpt;
+    const uint32_t nr = (uint32_t)(nrows - j0 < rpt ? nrows - j0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
+      const uint64_t j = j0 + w.r;
+      const uint64_t key = keys[j];
+      const uint64_t row = to ? (uint64_t)to[j] : j;
+      if constexpr (VEC) {
+        dst[row * upr + w.c] = InitUnit<DT, true>::make(key, w.c, spec);
+      } else {
+        float v[4];
+        init_block(key, w.c, spec, v);
+        const uint32_t c0 = 4 * w.c;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (c0 + k < width) dst[row * width + c0 + k] = InitUnit<DT, false>::bits(v[k]);
+      }
+    }
+  }
+}
+
+// k_rows_read for a table with an initializer: the same walk, and a unit whose
+// slot is kAbsent is made from its key (q[i], loaded by absent lanes only) in
+// the place where k_rows_read leaves zeros — the bytes an insert would store.
+// found[i] is still 0.  The present rows' loads are issued as they were, before
+// the first block is computed.  VEC: 16-B units; else single elements, each
+// absent element computing its own block (a lookup's absent ids are the
+// exception; the insert's fill is the path that shares a block).
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void k_rows_read_init(const typename InitUnit<DT, VEC>::U* __restrict__ R,
+                                                        const uint32_t* __restrict__ slots,
+                                                        const uint64_t* __restrict__ q,
+                                                        typename InitUnit<DT, VEC>::U* __restrict__ out,
+                                                        uint8_t* __restrict__ found, uint64_t n, uint32_t upr,
+                                                        uint32_t rpt, const int* __restrict__ gate, InitSpec spec) {
+  using U = typename InitUnit<DT, VEC>::U;
+  using UNIT = ReadUnit<U>;
+  constexpr int UN = UNIT::kDepth;
+  if (gate[R_RANGE]) return;
+  const uint64_t ntiles = (n + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t i0 = t * rpt;
+    const uint32_t nr = (uint32_t)(n - i0 < rpt ? n - i0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e0 = threadIdx.x; e0 < total; e0 += UN * kBlock) {
+      UNIT u[UN] = {};
+      uint64_t ro[UN] = {};  // the unit's offset in the reply
+      uint64_t key[UN] = {};
+      uint32_t col[UN] = {};
+      bool ok[UN];
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        ok[k] = e0 + (uint32_t)k * kBlock < total;
+        if (ok[k]) {
+          const uint64_t i = i0 + w.r;
+          u[k].locate(slots[i], w.c, upr);
+          ro[k] = i * upr + w.c;
+          col[k] = w.c;
+          if (!u[k].present) key[k] = q[i];
+          if (found && w.c == 0) found[i] = u[k].present ? 1 : 0;
+        }
+        w.next();
+      }
+#pragma unroll
+      for (int k = 0; k < UN; ++k)
+        if (ok[k]) u[k].load_state(R);
+#pragma unroll
+      for (int k = 0; k < UN; ++k) {
+        if (!ok[k]) continue;
+        if (!u[k].present) u[k].s = InitUnit<DT, VEC>::make(key[k], col[k], spec);
+        u[k].reply(out, ro[k]);
+      }
+    }
+  }
+}
+
+// k_rows_pool for a table with an initializer: the same chain (slot two ahead,
+// row unit one ahead), and the unit "one ahead" of an absent slot is made from
+// its key where k_rows_pool loads nothing; every position of the bag then adds
+// (times its weight, for kPoolWeighted), so a pooled lookup is the sum the
+// model will see once the update has inserted the id.  Only absent lanes load a
+// key and compute blocks.
+template <int DT, bool VEC, int POOL>
+__global__ __launch_bounds__(256) void k_rows_pool_init(const typename PoolAcc<DT, VEC>::U* __restrict__ R,
+                                                        const uint32_t* __restrict__ slots,
+                                                        const uint64_t* __restrict__ q,
+                                                        const uint64_t* __restrict__ offsets,
+                                                        typename PoolAcc<DT, VEC>::U* __restrict__ out, uint64_t nb,
+                                                        uint32_t upr, uint32_t rpt, const int* __restrict__ gate,
+                                                        const float* __restrict__ weights, InitSpec spec) {
+  using ACC = PoolAcc<DT, VEC>;
+  using U = typename ACC::U;
+  using INIT = InitUnit<DT, VEC>;
+  static_assert(sizeof(U) == sizeof(typename INIT::U), "one unit size");
+  if (gate[R_RANGE] | gate[R_OFFSETS]) return;
+  const uint64_t ntiles = (nb + rpt - 1) / rpt;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t b0 = t * rpt;
+    const uint32_t nr = (uint32_t)(nb - b0 < rpt ? nb - b0 : rpt);
+    const uint32_t total = nr * upr;
+    RowWalk w(threadIdx.x, upr);
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock, w.next()) {
+      const uint64_t b = b0 + w.r;
+      const uint32_t c = w.c;
+      uint32_t p = (uint32_t)offsets[b];  // <= n <= 2^32 - 2: checked
+      const uint32_t pe = (uint32_t)offsets[b + 1];
+      [[maybe_unused]] const uint32_t len = pe - p;
+      auto unit_at = [&](uint32_t slot, uint32_t pos) -> U {
+        if (slot != kAbsent) return R[(uint64_t)slot * upr + c];
+        return __builtin_bit_cast(U, INIT::make(q[pos], c, spec));
+      };
+      typename ACC::A acc = {};  // +0
+      if (p < pe) {
+        uint32_t s1 = p + 1 < pe ? slots[p + 1] : kAbsent;
+        [[maybe_unused]] float w0 = 0, w1 = 0;
+        if constexpr (POOL == kPoolWeighted) {
+          w0 = weights[p];
+          if (p + 1 < pe) w1 = weights[p + 1];
+        }
+        U v = unit_at(slots[p], p);
+        for (; p < pe; ++p) {
+          const uint32_t s2 = p + 2 < pe ? slots[p + 2] : kAbsent;
+          [[maybe_unused]] float w2 = 0;
+          if constexpr (POOL == kPoolWeighted)
+            if (p + 2 < pe) w2 = weights[p + 2];
+          U vn = {};
+          if (p + 1 < pe) vn = unit_at(s1, p + 1);
+          if constexpr (POOL == kPoolWeighted) {
+            acc = ACC::sum(acc, ACC::times(w0, v));
+            w0 = w1, w1 = w2;
+          } else {
+            acc = ACC::add(acc, v);
+          }
+          s1 = s2, v = vn;
         }
         if constexpr (POOL == kPoolMean) acc = ACC::over(acc, len);
       }
@@ -1424,7 +1666,27 @@ void publish_arrays(psg_table* t, DevBuf& K2, DevBuf& R2, DevBuf& M2, uint64_t s
   t->capacity = cap;
 }
 
-// Insert the keys of q that t->slots marks absent, each with a zero row.
+// ---- the initial rows: what the host passes ----------------------------------------
+inline bool has_init(const psg_table* t) { return t->init_kind == PSG_INIT_UNIFORM; }
+inline InitSpec init_spec(uint64_t seed, float lo, float hi) {
+  return {(uint32_t)seed, (uint32_t)(seed >> 32), lo, hi - lo};
+}
+inline InitSpec init_spec(const psg_table* t) { return init_spec(t->init_seed, t->init_lo, t->init_hi); }
+// what psg_table_set_init and psg_init_rows refuse of a uniform range, in the header's order
+int require_uniform(const char* name, float lo, float hi) {
+  PSG_REQUIRE(std::isfinite(lo) && std::isfinite(hi), PSG_ERR_INVALID, "%s: lo %g or hi %g is not finite", name, lo, hi);
+  PSG_REQUIRE(lo <= hi, PSG_ERR_INVALID, "%s: lo %g above hi %g", name, lo, hi);
+  const volatile float span = hi - lo;
+  PSG_REQUIRE(std::isfinite(span), PSG_ERR_INVALID, "%s: hi - lo is not finite in f32", name);
+  return PSG_OK;
+}
+// The initial rows of keys[0 .. nrows) into dst: row to[j], or row j where `to`
+// is null.  vec: rows of a multiple of 16 B that start on 16 B.
+int launch_init(int dtype, uint32_t width, void* dst, const uint64_t* keys, const uint32_t* to, uint64_t nrows,
+                bool vec, const InitSpec& spec, hipStream_t st);
+
+// Insert the keys of q that t->slots marks absent, each with a zero row or,
+// where the table has an initializer, its initial row.
 int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) {
   const uint64_t ntiles = compact_tiles(n);
   const SlotIs absent = {t->slots, kAbsent};
@@ -1454,7 +1716,11 @@ int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) 
                                                             (uint32_t*)old_to.p, (uint32_t*)new_to.p);
   PSG_HIP(hipGetLastError());
   if (S) PSG_TRY(move_rows(t, false, t->rows, R2.p, (const uint32_t*)old_to.p, S, st));
-  PSG_TRY(move_rows(t, false, nullptr, R2.p, (const uint32_t*)new_to.p, m, st));
+  if (has_init(t))
+    PSG_TRY(launch_init(t->dtype, t->width, R2.p, (const uint64_t*)miss.p, (const uint32_t*)new_to.p, m,
+                        row_bytes % 16 == 0, init_spec(t), st));
+  else
+    PSG_TRY(move_rows(t, false, nullptr, R2.p, (const uint32_t*)new_to.p, m, st));
   if (t->adam) {  // the moment rows go where their value rows went: 2 * width doubles = width 16-B units
     if (S) PSG_TRY(launch_move<u32x4>(false, t->mom, M2.p, (const uint32_t*)old_to.p, S, t->width, st));
     PSG_TRY(launch_move<u32x4>(false, nullptr, M2.p, (const uint32_t*)new_to.p, m, t->width, st));
@@ -1614,6 +1880,23 @@ int with_dtype(int dtype, F&& f) {
   }
 }
 
+int launch_init(int dtype, uint32_t width, void* dst, const uint64_t* keys, const uint32_t* to, uint64_t nrows,
+                bool vec, const InitSpec& spec, hipStream_t st) {
+  return with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    const uint32_t upr = vec ? width / Elem<DT>::kVec : (width + 3) / 4;  // 16-B units, or blocks of four elements
+    const Tiles g = tiles_for(nrows, upr);
+    if (vec)
+      k_rows_init<DT, true><<<g.grid, kBlock, 0, st>>>((typename InitUnit<DT, true>::U*)dst, keys, to, nrows, width, upr,
+                                                       g.rpt, spec);
+    else
+      k_rows_init<DT, false><<<g.grid, kBlock, 0, st>>>((typename InitUnit<DT, false>::U*)dst, keys, to, nrows, width,
+                                                        upr, g.rpt, spec);
+    PSG_HIP(hipGetLastError());
+    return (int)PSG_OK;
+  });
+}
+
 int accumulate(psg_table* t, int op, const AnyPlan* p, const void* vals, void* out, uint64_t n, hipStream_t st) {
   const bool vec = accumulate_vec(t, op, vals, out);
   return with_dtype(t->dtype, [&](auto dt) {
@@ -1738,6 +2021,18 @@ int launch_read(psg_table* t, void* out, uint8_t* found, uint64_t n, uint32_t up
   return PSG_OK;
 }
 
+// the lookup of a table with an initializer: absent ids answer with their initial rows
+template <int DT, bool VEC>
+int launch_read_init(psg_table* t, const uint64_t* keys, void* out, uint8_t* found, uint64_t n, uint32_t upr,
+                     hipStream_t st) {
+  using U = typename InitUnit<DT, VEC>::U;
+  const Tiles g = tiles_for(n, upr);
+  k_rows_read_init<DT, VEC><<<g.grid, kBlock, 0, st>>>((const U*)t->rows, t->slots, keys, (U*)out, found, n, upr, g.rpt,
+                                                       t->gate, init_spec(t));
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
 // ---- the merged update: dispatch --------------------------------------------------
 // The same-list walk over the n rows of list 0 (plan null), or the merge walk
 // over the plan's unique rows.
@@ -1818,6 +2113,27 @@ int launch_pool(psg_table* t, const uint64_t* offsets, const float* weights, int
   return PSG_OK;
 }
 
+// launch_pool for a table with an initializer
+template <int DT, bool VEC>
+int launch_pool_init(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* weights, int pool,
+                     void* out, uint64_t nb, uint32_t upr, hipStream_t st) {
+  using U = typename PoolAcc<DT, VEC>::U;
+  const Tiles g = tiles_for(nb, upr);
+  const InitSpec spec = init_spec(t);
+  auto launch = [&](auto mode) {
+    k_rows_pool_init<DT, VEC, decltype(mode)::value><<<g.grid, kBlock, 0, st>>>(
+        (const U*)t->rows, t->slots, keys, offsets, (U*)out, nb, upr, g.rpt, t->gate, weights, spec);
+  };
+  if (pool == kPoolWeighted)
+    launch(std::integral_constant<int, kPoolWeighted>{});
+  else if (pool == kPoolMean)
+    launch(std::integral_constant<int, kPoolMean>{});
+  else
+    launch(std::integral_constant<int, kPoolSum>{});
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
 int lookup_pooled(const char* name, psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* weights,
                   int mode, void* out, uint64_t n, uint64_t nb, psg_stream stream) {
   PSG_TRY(pooled_args(name, t, keys, offsets, out, "out", n, nb));
@@ -1834,6 +2150,10 @@ int lookup_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
   const bool vec = accumulate_vec(t, PSG_PULL, nullptr, out);
   PSG_TRY(with_dtype(t->dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
+    if (has_init(t)) {
+      if (vec) return launch_pool_init<DT, true>(t, keys, offsets, weights, pool, out, nb, t->width / Elem<DT>::kVec, st);
+      return launch_pool_init<DT, false>(t, keys, offsets, weights, pool, out, nb, t->width, st);
+    }
     if (vec) return launch_pool<DT, true>(t, offsets, weights, pool, out, nb, t->width / Elem<DT>::kVec, st);
     return launch_pool<DT, false>(t, offsets, weights, pool, out, nb, t->width, st);
   }));
@@ -2190,6 +2510,52 @@ int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* cons
   return PSG_OK;
 }
 
+// ---- the initial rows ---------------------------------------------------------------
+int psg_table_set_init(psg_table* t, int kind, uint64_t seed, float lo, float hi) {
+  const char* name = "psg_table_set_init";
+  PSG_TRY(require_table(name, t));
+  PSG_REQUIRE(kind == PSG_INIT_ZERO || kind == PSG_INIT_UNIFORM, PSG_ERR_INVALID, "%s: kind %d is no initializer", name,
+              kind);
+  PSG_REQUIRE(!t->init_set, PSG_ERR_INVALID, "%s: the table already has an initializer", name);
+  PSG_TRY(require_uniform(name, lo, hi));
+  t->init_set = 1;
+  t->init_kind = kind;
+  t->init_seed = seed;
+  t->init_lo = lo;
+  t->init_hi = hi;
+  return PSG_OK;
+}
+
+int psg_table_get_init(psg_table* t, int* kind, uint64_t* seed, float* lo, float* hi) {
+  PSG_REQUIRE(t && kind, PSG_ERR_INVALID, "psg_table_get_init: null argument");
+  *kind = t->init_kind;
+  if (seed) *seed = t->init_seed;
+  if (lo) *lo = t->init_lo;
+  if (hi) *hi = t->init_hi;
+  return PSG_OK;
+}
+
+int psg_init_rows(void* out, const uint64_t* keys, uint64_t n, int dtype, uint32_t width, uint64_t seed, float lo,
+                  float hi, psg_stream stream) {
+  const char* name = "psg_init_rows";
+  const int es = dtype_size(dtype);
+  PSG_REQUIRE(es > 0, PSG_ERR_INVALID, "%s: bad dtype %d", name, dtype);
+  PSG_REQUIRE(width >= 1 && width <= 4096, PSG_ERR_INVALID, "%s: width %u outside [1, 4096]", name, width);
+  PSG_REQUIRE(out || n == 0, PSG_ERR_INVALID, "%s: null out", name);
+  PSG_REQUIRE(keys || n == 0, PSG_ERR_INVALID, "%s: null keys", name);
+  PSG_REQUIRE((reinterpret_cast<uintptr_t>(out) & (uintptr_t)(es - 1)) == 0, PSG_ERR_INVALID,
+              "%s: out not on an element boundary", name);
+  PSG_TRY(require_uniform(name, lo, hi));
+  PSG_TRY(require_count(name, n));
+  if (n == 0) return PSG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = ((uint64_t)width * es) % 16 == 0 && aligned16(out);
+  PSG_TRY(launch_init(dtype, width, out, keys, nullptr, n, vec, init_spec(seed, lo, hi), st));
+  // complete on return: keys no longer read, out in memory
+  PSG_HIP(hipStreamSynchronize(st));
+  return PSG_OK;
+}
+
 int psg_table_get_adam(psg_table* t, int* has_adam, double* params4) {
   PSG_REQUIRE(t && has_adam, PSG_ERR_INVALID, "psg_table_get_adam: null argument");
   *has_adam = t->adam;
@@ -2260,9 +2626,18 @@ int psg_table_lookup(psg_table* t, const uint64_t* keys, void* out, uint8_t* fou
   PSG_TRY(launch_resolve(t, keys, n, t->gate, false, st));
   // presence alone (out null) has no unit: it is launched as one 16-B unit a row
   const uint32_t row_bytes = out ? t->width * (uint32_t)t->esize : 16;
-  PSG_TRY(for_raw_unit(out ? request_unit_bytes(t, PSG_PULL, nullptr, out) : 16, [&](auto u) {
-    return launch_read<decltype(u)>(t, out, found, n, row_bytes / (uint32_t)sizeof(u), st);
-  }));
+  if (has_init(t) && out) {  // presence alone is the same with and without an initializer
+    const bool vec = accumulate_vec(t, PSG_PULL, nullptr, out);
+    PSG_TRY(with_dtype(t->dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (vec) return launch_read_init<DT, true>(t, keys, out, found, n, t->width / Elem<DT>::kVec, st);
+      return launch_read_init<DT, false>(t, keys, out, found, n, t->width, st);
+    }));
+  } else {
+    PSG_TRY(for_raw_unit(out ? request_unit_bytes(t, PSG_PULL, nullptr, out) : 16, [&](auto u) {
+      return launch_read<decltype(u)>(t, out, found, n, row_bytes / (uint32_t)sizeof(u), st);
+    }));
+  }
   // the one synchronisation: keys no longer read, the reply in memory, the flags on the host
   PSG_TRY(gate_end(t, st));
   return require_in_range(t);

@@ -15,7 +15,8 @@
 //
 // The rows live in a psg_table over [0, kMaxKey), created on the first
 // request (or by SaveModel / LoadModel, below); an absent key is inserted with
-// a zero row.  By default keys must be
+// a zero row or, after SetInit, with its seeded initial row
+// (psg_table_set_init).  By default keys must be
 // strictly ascending (the KVPairs contract, KVApp.h:23): a list out of order or
 // with repeats fails the request's CHECK.  With any_order set the handle calls
 // psg_table_handle_any, which serves such a list in arrival order, every
@@ -68,14 +69,38 @@ constexpr int kRowErase = 4;
 
 namespace detail {
 
+// What the three row handles' SetInit(seed, lo, hi) keeps until the table is
+// created: every new row starts from a uniform value in [lo, hi] that depends
+// on (seed, key, column) alone (psg_table_set_init) instead of from zero, and
+// kRowLookup and the pooled lookups answer a key the table does not hold with
+// that row.  Called before the first request, with the same triple on every
+// server: a row then does not depend on the number of servers.  The checkpoint
+// file does not carry the triple (like the Adam parameters, it is the
+// caller's to set again): a job resumed with the same triple is the
+// uninterrupted job bit for bit, with another one the keys it has not seen yet
+// start elsewhere.
+struct RowInit {
+  bool set = false;
+  uint64_t seed = 0;
+  float lo = 0.f, hi = 0.f;
+  void Set(const char* who, psg_table* table, uint64_t seed_, float lo_, float hi_) {
+    CHECK(!table) << who << "::SetInit comes before the first request, SaveModel or LoadModel: the table exists";
+    CHECK(!set) << who << "::SetInit was called twice";
+    set = true, seed = seed_, lo = lo_, hi = hi_;
+  }
+};
+
 // The row handles' table, created on first use (a request, SaveModel or
 // LoadModel): [0, kMaxKey), no rows allocated; with_adam gives it the moments
-// of Adam(learning_rate), as LRServer.h:83-84 constructs it.
+// of Adam(learning_rate), as LRServer.h:83-84 constructs it; init, where set,
+// its initializer.
 inline psg_table* EnsureRowTable(psg_table** table, int dtype, uint32_t width, bool with_adam = false,
-                                 float learning_rate = 0.f) {
+                                 float learning_rate = 0.f, const RowInit* init = nullptr) {
   if (*table) return *table;
   device::Check(psg_table_create(dtype, width, 0, kMaxKey, 0, table), "psg_table_create");
   if (with_adam) device::Check(psg_table_set_adam(*table, (double)learning_rate, 0.9, 0.999, 1e-8), "psg_table_set_adam");
+  if (init && init->set)
+    device::Check(psg_table_set_init(*table, PSG_INIT_UNIFORM, init->seed, init->lo, init->hi), "psg_table_set_init");
   return *table;
 }
 
@@ -240,6 +265,7 @@ struct KVServerRowHandle {
     psg_table* table = nullptr;
     uint32_t width = 0;
     bool any_order = false;
+    detail::RowInit init;
     ~State() {
       if (table) psg_table_destroy(table);
     }
@@ -261,7 +287,7 @@ struct KVServerRowHandle {
     CHECK_GE(dt, 0) << "KVServerRowHandle: value type not supported by the HBM table";
     CHECK(req_data.lens.empty()) << "KVServerRowHandle: rows have one fixed width, lens are not supported";
     detail::RefusePooledUpdate("KVServerRowHandle", req_meta);
-    detail::EnsureRowTable(&state->table, dt, state->width);
+    Table();
     if (detail::ServeRowLifecycle("KVServerRowHandle", state->table, req_meta, req_data, server, w)) return;
     const int flags = (req_meta.push ? PSG_PUSH : 0) | (req_meta.pull ? PSG_PULL : 0);
     if (req_meta.push) CHECK_EQ(n * w, req_data.vals.size()) << "a Push carries width values per key";
@@ -280,18 +306,21 @@ struct KVServerRowHandle {
   // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
   size_t size() const { return detail::RowTableSize(state->table); }
 
+  // New rows start from seeded uniform values in [lo, hi] (detail::RowInit above)
+  void SetInit(uint64_t seed, float lo, float hi) { state->init.Set("KVServerRowHandle", state->table, seed, lo, hi); }
+
   // The table to a file and back (ps/row_checkpoint.h; the reference's
   // SaveModel / USE_OLD_MODEL, LRServer.h:107-115, 36-63).  Called on the server
   // node between barriers, with no request in flight.  LoadModel assigns the
   // keys of this server's own range and returns their number: call it once per
   // saved shard, whatever the number of servers that saved.  An accumulate
   // handle has no iteration: it saves 0.
-  void SaveModel(const std::string& path) {
-    SaveRowTable(detail::EnsureRowTable(&state->table, device::DType<Value>(), state->width), 0, path);
-  }
-  int LoadModel(const std::string& path) {
-    return detail::LoadOwnRows(detail::EnsureRowTable(&state->table, device::DType<Value>(), state->width), path,
-                               nullptr);
+  void SaveModel(const std::string& path) { SaveRowTable(Table(), 0, path); }
+  int LoadModel(const std::string& path) { return detail::LoadOwnRows(Table(), path, nullptr); }
+
+ private:
+  psg_table* Table() {
+    return detail::EnsureRowTable(&state->table, device::DType<Value>(), state->width, false, 0.f, &state->init);
   }
 };
 

@@ -62,6 +62,7 @@ struct KVServerRowOptHandle {
     bool use_adam = false;
     int iteration = 0;
     bool any_order = false;
+    detail::RowInit init;
     ~State() {
       if (table) psg_table_destroy(table);
     }
@@ -134,6 +135,8 @@ struct KVServerRowOptHandle {
   }
 
   int iteration() const { return state->iteration; }
+  // New rows start from seeded uniform values in [lo, hi] (detail::RowInit, ps/row_handle.h)
+  void SetInit(uint64_t seed, float lo, float hi) { state->init.Set("KVServerRowOptHandle", state->table, seed, lo, hi); }
   // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
   size_t size() const { return detail::RowTableSize(state->table); }
 
@@ -148,7 +151,7 @@ struct KVServerRowOptHandle {
 
  private:
   psg_table* Table() {
-    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr);
+    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr, &state->init);
   }
 };
 

@@ -59,7 +59,7 @@
 // round's requests.  A round merges at most 16 requests: more workers fail the
 // handle's CHECK.  The rows live in a psg_table over [0, kMaxKey), created on
 // the first request (or by SaveModel / LoadModel); an absent key starts from a
-// zero row and zero moments.
+// zero row (after SetInit: its seeded initial row, psg_table_set_init) and zero moments.
 // Adam gets ((double)learning_rate, 0.9, 0.999, 1e-8), as LRServer.h:83-84
 // constructs it.  Register with KVServer::SetDeviceRequestHandle; host frames
 // are staged into HBM.
@@ -96,6 +96,7 @@ struct KVServerRowSyncHandle {
     bool use_adam = false;
     int iteration = 0;
     std::vector<Held> held;
+    detail::RowInit init;
     ~State() {
       if (table) psg_table_destroy(table);
     }
@@ -172,6 +173,8 @@ struct KVServerRowSyncHandle {
   }
 
   int iteration() const { return state->iteration; }
+  // New rows start from seeded uniform values in [lo, hi] (detail::RowInit, ps/row_handle.h)
+  void SetInit(uint64_t seed, float lo, float hi) { state->init.Set("KVServerRowSyncHandle", state->table, seed, lo, hi); }
   // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
   size_t size() const { return detail::RowTableSize(state->table); }
 
@@ -189,7 +192,7 @@ struct KVServerRowSyncHandle {
 
  private:
   psg_table* Table() {
-    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr);
+    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr, &state->init);
   }
 
   // LRServer.h:163-178: the update on the merged gradients, then every held answer

@@ -29,6 +29,7 @@ PUSH, PULL = 1, 2
 RUN_ONE_BY_ONE, RUN_SAME_LIST, RUN_STRIDED = 0, 1, 2
 MERGED_SAME_LIST, MERGED_SORTED = 1, 2
 POOL_SUM, POOL_MEAN = 0, 1
+INIT_ZERO, INIT_UNIFORM = 0, 1
 H2D, D2H, D2D = 0, 1, 2
 
 _NP = {F32: np.float32, F64: np.float64, F16: np.float16, BF16: np.uint16}
@@ -55,6 +56,7 @@ EXPORTS = [
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
     "psg_table_lookup_pooled_weighted", "psg_table_update_pooled_weighted", "psg_table_update_pooled_merged",
+    "psg_table_set_init", "psg_table_get_init", "psg_init_rows",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
     "psg_pool_reduce_mean", "psg_pool_scale_mean",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
@@ -176,6 +178,9 @@ def lib() -> C.CDLL:
             "psg_table_lookup_pooled_weighted": ([vp, vp, vp, vp, i32, vp, u64, u64, vp], i32),
             "psg_table_update_pooled_weighted": ([vp, vp, vp, vp, i32, vp, u64, u64, f32, i32, vp], i32),
             "psg_table_update_pooled_merged": ([vp, i32, vp, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
+            "psg_table_set_init": ([vp, i32, u64, f32, f32], i32),
+            "psg_table_get_init": ([vp, C.POINTER(i32), C.POINTER(u64), C.POINTER(f32), C.POINTER(f32)], i32),
+            "psg_init_rows": ([vp, vp, u64, i32, C.c_uint32, u64, f32, f32, vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -222,8 +227,13 @@ def lib() -> C.CDLL:
             "psg_node_barrier_create": ([C.c_char_p, i32, i32, C.POINTER(vp)], i32),
             "psg_node_barrier_wait": ([vp, f64], i32), "psg_node_barrier_destroy": ([vp], i32),
         }
+        # PSG_LIB_OLDER=1 (measurement tools that load a library built from an older
+        # commit, tools/rows_init_bench.py): a symbol it does not have yet is left unbound
+        older = os.environ.get("PSG_LIB_OLDER") == "1"
         for name, (args, res) in sig.items():
-            fn = getattr(L, name)
+            fn = getattr(L, name, None) if older else getattr(L, name)
+            if fn is None:
+                continue
             fn.argtypes = args
             fn.restype = res
         _lib = L
@@ -573,6 +583,19 @@ class Table:
         """Adam moments (f64, zero) beside every row; an update then runs Adam.h:28-34."""
         _call("psg_table_set_adam", self.h, lr, beta1, beta2, eps)
 
+    def set_init(self, seed: int, lo: float, hi: float, kind: int = INIT_UNIFORM) -> None:
+        """What a new row starts from (psg_table_set_init): a uniform value in
+        [lo, hi] that depends on (seed, key, column) alone, in place of zero.  Once
+        per table, before its first request."""
+        _call("psg_table_set_init", self.h, kind, seed, lo, hi)
+
+    def init(self):
+        """(kind, seed, lo, hi) as set_init got them; (INIT_ZERO, 0, 0.0, 0.0) on a
+        table it was never called on (psg_table_get_init)."""
+        kind, seed, lo, hi = C.c_int(0), C.c_uint64(0), C.c_float(0), C.c_float(0)
+        _call("psg_table_get_init", self.h, C.byref(kind), C.byref(seed), C.byref(lo), C.byref(hi))
+        return kind.value, seed.value, lo.value, hi.value
+
     def update(self, flags: int, keys, grads, out, n: int, lr: float, iteration: int, stream=None) -> None:
         """One gradient request (psg_table_update): SGD, or Adam after set_adam, on
         the rows of n ascending device keys; grads / out: n * width floats."""
@@ -692,6 +715,12 @@ class Table:
             self.close()
         except Exception:
             pass
+
+
+def init_rows(out, keys, n: int, dtype: int, width: int, seed: int, lo: float, hi: float, stream=None) -> None:
+    """The initial rows of n device keys under (seed, lo, hi), no table involved
+    (psg_init_rows): n * width elements of dtype into the device array out."""
+    _call("psg_init_rows", _ptr(out), _ptr(keys), n, dtype, width, seed, lo, hi, _s(stream))
 
 
 # ---- worker side --------------------------------------------------------------
