@@ -614,6 +614,48 @@ int psg_table_dump_moments(psg_table* t, double* m_host, double* v_host);
  * epsilon (zeros without Adam state).  Host only. */
 int psg_table_get_adam(psg_table* t, int* has_adam, double* params4);
 
+/* Give an F32 table row-wise Adagrad state: ONE f64 accumulator per row (not per
+ * element), A[capacity] in slot order in HBM beside the rows; initial_accumulator
+ * for every row present and for every row inserted later.  Every update call
+ * (psg_table_update, _update_any, _update_merged on both paths, _update_pooled,
+ * _update_pooled_weighted, _update_pooled_merged) then takes the step below
+ * wherever it takes an SGD step today.  s[c] is the f32 gradient the call defines
+ * for that step — an occurrence's gradient row for psg_table_update / _update_any
+ * (one step per occurrence, the accumulator advancing each time), the per-key sum
+ * from +0.0f in arrival order for the merged and pooled calls (one step per key) —
+ * and lr the call's f32 argument:
+ *   g[c] = (double)(lr * s[c])                  c < width  -- f32 product, widened
+ *   y[c] = g[c] * g[c] for c < width, +0.0 for width <= c < P,  P = width rounded up
+ *          to a power of two
+ *   for h = P/2, P/4, ..., 1:  y[c] = y[c] + y[c + h] for c < h   -- f64 adds, this tree
+ *   A    = A + y[0] / (double)width
+ *   step = learning_rate / (sqrt(A) + epsilon)
+ *   row[c] = (float)((double)row[c] - step * g[c])   -- one f64 multiply, one f64 subtract, never fused
+ * and a PSG_PULL reply is the updated row, as ever.  g * g is exact in f64, so only
+ * the tree's adds round, and the tree fixes their order: the bits depend neither on
+ * how `grads` is aligned, nor on the row's slot, the number of servers or a restart.
+ * sqrt and / are the correctly rounded f64 operations.  Nothing is special-cased:
+ * epsilon == 0 with a zero accumulator and a zero gradient row gives what the
+ * arithmetic gives, NaN rows.  `iteration` is checked as ever and not used.
+ * The accumulators follow their rows through inserts, growth and psg_table_erase;
+ * psg_table_clear drops them and keeps the setting.  psg_table_assign leaves a
+ * present key's accumulator alone and gives an inserted key initial_accumulator;
+ * psg_table_export has rows only (m / v stay refused); lookups never read A.
+ * Refused before any device call, in this order: a null table -> PSG_ERR_INVALID;
+ * a non-F32 table -> PSG_ERR_UNSUPPORTED; a table that already has Adam or Adagrad
+ * state; learning_rate not finite; epsilon negative or not finite;
+ * initial_accumulator negative or not finite -> PSG_ERR_INVALID.  psg_table_set_adam
+ * on an Adagrad table fails with PSG_ERR_INVALID. */
+int psg_table_set_adagrad(psg_table* t, double learning_rate, double epsilon,
+                          double initial_accumulator);
+/* Whether the table has Adagrad state (*has: 0 / 1) and, where params3 is not NULL,
+ * the three values psg_table_set_adagrad got: learning_rate, epsilon,
+ * initial_accumulator (zeros without Adagrad state).  Host only. */
+int psg_table_get_adagrad(psg_table* t, int* has, double* params3);
+/* The Adagrad accumulators in key order, info.size doubles.  Fails with
+ * PSG_ERR_INVALID on a table without Adagrad state.  Synchronous. */
+int psg_table_dump_accum(psg_table* t, double* acc_host);
+
 /* What a NEW row starts from.  The reference's store[key] value-initialises to
  * zero (src/ps/KVApp.h:446-454), and so does a table by default; a model that
  * multiplies two looked-up rows never leaves the origin from there, so a table

@@ -79,6 +79,15 @@
 // frames' gradient arrays laid end to end (k_bag_of / k_row_index from each
 // frame's first row), and k_rows_walk_pool picking the frame's array with
 // frame_of, as k_rows_walk_merge does.
+//
+// Row-wise Adagrad (psg_table_set_adagrad) is the one optimizer whose step needs
+// the whole row: one f64 accumulator per row, A[S] in slot order, advanced by the
+// mean of the squares of the row's merged gradient before any column moves.  No
+// walk above can take it (a lane owns a unit and never talks to its neighbours),
+// so every update call on an Adagrad table forks in pass 2 to k_rows_walk_rowwise:
+// a group of up to 64 lanes owns a unique row, sums the squares in a fixed tree
+// (in-lane adds, then a shuffle butterfly over the group) and steps the row.  A
+// follows its rows through insert, growth and erase as rows of one 8-B unit.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -105,6 +114,11 @@ struct psg_table {
   int adam;
   double alr, beta1, beta2, eps;
   double* mom;
+  // row-wise Adagrad state (psg_table_set_adagrad): its three parameters and one
+  // accumulator per row, capacity doubles in slot order (null while capacity == 0)
+  int adagrad;
+  double ag_lr, ag_eps, ag_init;
+  double* accum;
   // scratch of the order-preserving requests (psg_table_*_any): the sort's
   // buffers, perm, U and seg carved from one block grown on demand
   void* any_buf;
@@ -1452,6 +1466,263 @@ __global__ __launch_bounds__(256) void k_rows_walk_pool(typename UNIT::U* __rest
   }
 }
 
+// ---- row-wise Adagrad (psg_table_set_adagrad) -----------------------------------
+// One f64 accumulator per ROW, A[slot].  A step on a row takes the gradient s[c]
+// the call defines for it (include/psg.h):
+//   g[c] = (double)(lr * s[c]);  y[c] = g[c] * g[c], +0 from width up to P (a power of two)
+//   for h = P/2 .. 1:  y[c] += y[c + h] for c < h      -- this tree, no other order
+//   A += y[0] / width;  step = alr / (sqrt(A) + eps);  row[c] = (float)((double)row[c] - step * g[c])
+// so no column may change before the whole row's gradient was seen: a lane that
+// owns one unit of a row (every walk above) cannot take this step.  Here a GROUP
+// of G = 2^lg lanes (G <= 64, so inside one wave) owns one unique row; lane l of
+// the group holds units l, l + G, l + 2G, ... of it, UPL of them (a compile-time
+// bound: gradient, sum and row live in registers, no LDS, no scratch).  A unit is
+// four columns (VEC, 16 B) or one.  The tree, by the stride of its levels:
+//   h >= G units   in-lane adds between the lane's own units (sq_tree below);
+//   G > h >= 1     a butterfly over the group, y += shfl_xor(y, h): the add
+//                  commutes, so every lane ends with the bits the tree defines;
+//   h = 2, 1 columns (VEC)   (y0 + y2) + (y1 + y3) inside the unit.
+// A unit, a lane or a level past the row's end holds +0.0, and y + +0.0 is y for
+// y >= 0: the bits do not depend on G, UPL, the unit or the slot.  A 256-thread
+// block serves 256 / G rows at a time.  Per step a row costs its gradient once,
+// the row read once (issued before the first gradient is) and written once, and
+// A[slot] read and written by lane 0 of the group.  One writer per row, no atomics.
+// MODE: kRowwiseEach, one step per occurrence and the running row as its reply
+// (psg_table_update, _update_any); kRowwiseSum, the occurrences summed from +0.0f
+// in arrival order, one step, the updated row to every occurrence's reply (the
+// merged round's sorted path and the pooled updates, whose factor per occurrence
+// is a weight or one over its bag's length); kRowwiseSame, the same-list round:
+// the occurrences of request row u are row u of each frame.
+struct RowwiseArgs {
+  float lr;                // the call's, multiplied onto the gradient in f32
+  double alr, eps, width;  // learning_rate, epsilon, (double)width
+};
+struct RowwiseSrc {
+  const uint32_t* seg;      // the bounds of unique row u's occurrences; null: its one occurrence is position u
+  const uint32_t* idx;      // the gradient row of position p (perm, bags); null: p itself
+  const float* grads;       // the one gradient array; null: the round's frames
+  float* out;               // kRowwiseEach: the reply array
+  const float* w;           // kRowwiseSum: a factor per position (weighted bags)
+  const uint64_t* offsets;  // kRowwiseSum: the bags whose length divides their gradient row (mean bags)
+  Frames f;
+};
+enum { kRowwiseEach = 0, kRowwiseSum = 1, kRowwiseSame = 2 };
+
+// No packed f32 arithmetic in this kernel, its lambdas and sq_tree (v_pk_mul_f32
+// and its kin): the f32 products and sums are written, and built, one at a time.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+// The in-lane levels of the tree over a lane's UPL units: y[k] += y[k + h] for
+// h = UPL/2 .. 1 is, read from its last add, (the even k) + (the odd k), each
+// half the same tree again over stride 2S: evaluated depth first, log2(UPL)
+// partial sums are alive instead of UPL squares.
+template <int S, int O, int UPL, int E, typename F>
+__device__ __forceinline__ void sq_tree(const F& sq, double y[E]) {
+  if constexpr (S >= UPL) {
+    sq(O, y);
+  } else {
+    double b[E];
+    sq_tree<2 * S, O, UPL, E>(sq, y);
+    sq_tree<2 * S, O + S, UPL, E>(sq, b);
+#pragma unroll
+    for (int e = 0; e < E; ++e) y[e] = y[e] + b[e];
+  }
+}
+
+template <bool VEC, int UPL, int MODE, bool PULL>
+__global__ __launch_bounds__(256) void k_rows_walk_rowwise(float* __restrict__ R, double* __restrict__ A,
+                                                           const uint32_t* __restrict__ slots, RowwiseSrc src,
+                                                           uint64_t m, uint32_t upr, uint32_t lg, RowwiseArgs a) {
+  constexpr int E = VEC ? 4 : 1;
+  // the next occurrence's units are loaded before the current one is used while both fit
+  constexpr bool kAhead = UPL * E <= 16;
+  using U = typename std::conditional<VEC, f32x4, float>::type;
+  __shared__ uint64_t vals_at[kMaxFrames], out_at[kMaxFrames];
+  if (threadIdx.x < kMaxFrames) vals_at[threadIdx.x] = (uint64_t)src.f.vals[threadIdx.x];
+  else if (threadIdx.x < 2 * kMaxFrames) out_at[threadIdx.x - kMaxFrames] = (uint64_t)src.f.out[threadIdx.x - kMaxFrames];
+  __syncthreads();
+  const uint32_t G = 1u << lg;
+  const uint32_t l = threadIdx.x & (G - 1);
+  const uint32_t head = (threadIdx.x & 63u) & ~(G - 1);  // the group's lane 0 in its wave
+  const uint32_t gpb = kBlock >> lg;                     // groups, and rows at a time, per block
+  const uint32_t width = upr * E;
+  const int pool = src.w ? kPoolWeighted : src.offsets ? kPoolMean : kPoolSum;
+
+  // a row's units of this lane from / to `row`, the row's first element
+  auto load = [&](float (&x)[UPL][E], const float* row) {
+#pragma unroll
+    for (int k = 0; k < UPL; ++k) {
+      const uint32_t c = l + (uint32_t)k * G;
+      U v = {};
+      if (c < upr) v = reinterpret_cast<const U*>(row)[c];
+      if constexpr (VEC) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[k][e] = v[e];
+      } else {
+        x[k][0] = v;
+      }
+    }
+  };
+  auto store = [&](const float (&x)[UPL][E], float* row) {
+#pragma unroll
+    for (int k = 0; k < UPL; ++k) {
+      const uint32_t c = l + (uint32_t)k * G;
+      if (c >= upr) continue;
+      if constexpr (VEC) reinterpret_cast<U*>(row)[c] = f32x4{x[k][0], x[k][1], x[k][2], x[k][3]};
+      else row[c] = x[k][0];
+    }
+  };
+
+  const uint64_t stride = (uint64_t)gridDim.x * gpb;
+  uint64_t u = (uint64_t)blockIdx.x * gpb + (threadIdx.x >> lg);
+  uint32_t slot_next = u < m ? slots[u] : 0;
+  for (; u < m; u += stride) {
+    const uint32_t slot = slot_next;
+    if (u + stride < m) slot_next = slots[u + stride];  // the next row's slot, a row ahead
+    float* const rp = R + (uint64_t)slot * width;
+    // the row: issued here and used by the first step; a wide row that is summed
+    // first is issued behind the sum, in front of the tree that hides it
+    constexpr bool kRowFirst = kAhead || MODE == kRowwiseEach;
+    float r[UPL][E];
+    if constexpr (kRowFirst) load(r, rp);
+    double acc = 0.0;
+    if (l == 0) acc = A[slot];
+    uint32_t p0, pe;
+    if constexpr (MODE == kRowwiseSame) {
+      p0 = 0, pe = (uint32_t)src.f.k;
+    } else {
+      p0 = src.seg ? src.seg[u] : (uint32_t)u;
+      pe = src.seg ? src.seg[u + 1] : p0 + 1;  // > p0: every unique key has an occurrence
+    }
+    // position p's gradient row index, the row itself and its factor
+    auto index = [&](uint32_t p) -> uint32_t {
+      if constexpr (MODE == kRowwiseSame) return p;
+      else return src.idx ? src.idx[p] : p;
+    };
+    auto where = [&](uint32_t ix) -> const float* {
+      if constexpr (MODE == kRowwiseSame) return (const float*)vals_at[ix] + u * width;
+      if (src.grads) return src.grads + (uint64_t)ix * width;
+      return (const float*)vals_at[frame_of(src.f, ix)] + (uint64_t)ix * width;
+    };
+    auto factor = [&](uint32_t p, uint32_t ix) -> float {
+      if (pool == kPoolWeighted) return src.w[p];
+      if (pool == kPoolMean) return (float)(uint32_t)(src.offsets[(uint64_t)ix + 1] - src.offsets[ix]);
+      return 0.0f;
+    };
+    // one step on r with the gradient s; acc is the group's accumulator in every lane
+    auto step = [&](const float (&s)[UPL][E]) {
+      auto sq = [&](int k, double y[E]) {
+        const bool in = l + (uint32_t)k * G < upr;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const double g = (double)(a.lr * s[k][e]);
+          y[e] = in ? g * g : 0.0;
+        }
+      };
+      double y[E];
+      sq_tree<1, 0, UPL, E>(sq, y);
+#pragma unroll
+      for (uint32_t d = 32; d >= 1; d >>= 1) {
+        if (d >= G) continue;
+#pragma unroll
+        for (int e = 0; e < E; ++e) y[e] = y[e] + __shfl_xor(y[e], (int)d, 64);
+      }
+      double y0 = y[0];
+      if constexpr (VEC) y0 = (y[0] + y[2]) + (y[1] + y[3]);
+      acc = acc + y0 / a.width;
+      const double st = a.alr / (sqrt(acc) + a.eps);
+#pragma unroll
+      for (int k = 0; k < UPL; ++k)
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          float se = s[k][e];
+          // wide rows: the product is made again here, not kept as 2 * UPL * E more
+          // registers across the reduction
+          if constexpr (UPL * E > 16) asm volatile("" : "+v"(se));
+          const double g = (double)(a.lr * se);
+          const double d = st * g;
+          r[k][e] = (float)((double)r[k][e] - d);
+        }
+    };
+
+    uint32_t i0 = index(p0);
+    uint32_t i1 = p0 + 1 < pe ? index(p0 + 1) : 0;
+    float v[UPL][E];
+    load(v, where(i0));
+    [[maybe_unused]] float f = 0.0f;
+    if constexpr (MODE == kRowwiseSum) f = factor(p0, i0);
+    acc = __shfl(acc, (int)head, 64);
+    [[maybe_unused]] float s[UPL][E] = {};  // +0.0f: the merge buffer starts from zero
+    for (uint32_t p = p0; p < pe; ++p) {
+      const uint32_t i2 = p + 2 < pe ? index(p + 2) : 0;
+      [[maybe_unused]] float vn[UPL][E];
+      [[maybe_unused]] float fn = 0.0f;
+      if constexpr (kAhead) {
+        if (p + 1 < pe) {
+          load(vn, where(i1));
+          if constexpr (MODE == kRowwiseSum) fn = factor(p + 1, i1);
+        }
+      }
+      if constexpr (MODE == kRowwiseEach) {
+        step(v);
+        if constexpr (PULL) store(r, src.out + (uint64_t)i0 * width);
+      } else {
+#pragma unroll
+        for (int k = 0; k < UPL; ++k)
+#pragma unroll
+          for (int e = 0; e < E; ++e) {
+            float t = v[k][e];
+            if constexpr (MODE == kRowwiseSum) {
+              if (pool == kPoolWeighted) t = f * t;
+              else if (pool == kPoolMean) t = t / f;
+            }
+            s[k][e] = s[k][e] + t;
+          }
+      }
+      if (p + 1 < pe) {
+        if constexpr (kAhead) {
+#pragma unroll
+          for (int k = 0; k < UPL; ++k)
+#pragma unroll
+            for (int e = 0; e < E; ++e) v[k][e] = vn[k][e];
+          f = fn;
+        } else {
+          load(v, where(i1));
+          if constexpr (MODE == kRowwiseSum) f = factor(p + 1, i1);
+        }
+      }
+      i0 = i1, i1 = i2;
+    }
+    if constexpr (!kRowFirst) load(r, rp);
+    if constexpr (MODE != kRowwiseEach) step(s);
+    store(r, rp);
+    if (l == 0) A[slot] = acc;
+    if constexpr (PULL && MODE == kRowwiseSame) {
+      for (int j = 0; j < src.f.k; ++j) store(r, (float*)out_at[j] + u * width);
+    }
+    if constexpr (PULL && MODE == kRowwiseSum) {
+      uint32_t j0 = index(p0);
+      for (uint32_t p = p0; p < pe; ++p) {
+        const uint32_t jn = p + 1 < pe ? index(p + 1) : 0;
+        store(r, (float*)out_at[frame_of(src.f, j0)] + (uint64_t)j0 * width);
+        j0 = jn;
+      }
+    }
+  }
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
+// A[to[j]] (to null: A[j]) = value for j < n: the accumulators of new rows
+__global__ __launch_bounds__(256) void k_accum_fill(double* __restrict__ A, const uint32_t* __restrict__ to, uint64_t n,
+                                                    double value) {
+  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock)
+    A[to ? (uint64_t)to[j] : j] = value;
+}
+
 unsigned grid_for(uint64_t blocks) {
   const uint64_t cap = (uint64_t)max_stream_blocks();
   if (blocks > cap) blocks = cap;
@@ -1651,8 +1922,8 @@ struct DevBuf {  // a device scratch array freed on every return path
 };
 
 // New arrays of `size` rows in `cap` take the table's place (insert, erase);
-// the old ones are left in K2 / R2 / M2 and freed with them.
-void publish_arrays(psg_table* t, DevBuf& K2, DevBuf& R2, DevBuf& M2, uint64_t size, uint64_t cap) {
+// the old ones are left in K2 / R2 / M2 / A2 and freed with them.
+void publish_arrays(psg_table* t, DevBuf& K2, DevBuf& R2, DevBuf& M2, DevBuf& A2, uint64_t size, uint64_t cap) {
   void* old_keys = t->keys;
   t->keys = (uint64_t*)K2.p;
   K2.p = old_keys;
@@ -1661,6 +1932,11 @@ void publish_arrays(psg_table* t, DevBuf& K2, DevBuf& R2, DevBuf& M2, uint64_t s
     void* old_mom = t->mom;
     t->mom = (double*)M2.p;
     M2.p = old_mom;
+  }
+  if (t->adagrad) {
+    void* old_accum = t->accum;
+    t->accum = (double*)A2.p;
+    A2.p = old_accum;
   }
   t->size = size;
   t->capacity = cap;
@@ -1685,6 +1961,12 @@ int require_uniform(const char* name, float lo, float hi) {
 int launch_init(int dtype, uint32_t width, void* dst, const uint64_t* keys, const uint32_t* to, uint64_t nrows,
                 bool vec, const InitSpec& spec, hipStream_t st);
 
+int fill_accum(const psg_table* t, double* A, const uint32_t* to, uint64_t n, hipStream_t st) {
+  k_accum_fill<<<grid_per_lane(n), kBlock, 0, st>>>(A, to, n, t->ag_init);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
 // Insert the keys of q that t->slots marks absent, each with a zero row or,
 // where the table has an initializer, its initial row.
 int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) {
@@ -1708,10 +1990,11 @@ int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) 
   PSG_HIP(hipMalloc(&new_to.p, m * sizeof(uint32_t)));
   compact_emit(n, (const uint32_t*)counts.p, absent, EmitKey{q, (uint64_t*)miss.p}, st);
   PSG_HIP(hipGetLastError());
-  DevBuf K2, R2, M2;
+  DevBuf K2, R2, M2, A2;
   PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
   PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
   if (t->adam) PSG_HIP(hipMalloc(&M2.p, cap * mom_row_bytes(t)));
+  if (t->adagrad) PSG_HIP(hipMalloc(&A2.p, cap * sizeof(double)));
   k_rows_merge_keys<<<grid_per_lane(S + m), kBlock, 0, st>>>(t->keys, S, (const uint64_t*)miss.p, m, (uint64_t*)K2.p,
                                                             (uint32_t*)old_to.p, (uint32_t*)new_to.p);
   PSG_HIP(hipGetLastError());
@@ -1725,8 +2008,12 @@ int insert_missing(psg_table* t, const uint64_t* q, uint64_t n, hipStream_t st) 
     if (S) PSG_TRY(launch_move<u32x4>(false, t->mom, M2.p, (const uint32_t*)old_to.p, S, t->width, st));
     PSG_TRY(launch_move<u32x4>(false, nullptr, M2.p, (const uint32_t*)new_to.p, m, t->width, st));
   }
+  if (t->adagrad) {  // the accumulators likewise, as rows of one 8-B unit; a new row's is initial_accumulator
+    if (S) PSG_TRY(launch_move<uint64_t>(false, t->accum, A2.p, (const uint32_t*)old_to.p, S, 1, st));
+    PSG_TRY(fill_accum(t, (double*)A2.p, (const uint32_t*)new_to.p, m, st));
+  }
   PSG_HIP(hipStreamSynchronize(st));
-  publish_arrays(t, K2, R2, M2, S + m, cap);
+  publish_arrays(t, K2, R2, M2, A2, S + m, cap);
   return PSG_OK;
 }
 
@@ -1936,6 +2223,43 @@ int with_opt_unit(const psg_table* t, bool vec, float lr, int iteration, F&& f) 
   return vec ? with(UnitTag<OptUnit<false, true>>{}) : with(UnitTag<OptUnit<false, false>>{});
 }
 
+// ---- row-wise Adagrad: dispatch ------------------------------------------------------
+// k_rows_walk_rowwise over m unique rows: G = the row's units rounded up to a
+// power of two, 64 at most; UPL the units a lane then holds, rounded up to the
+// next instantiation (1, 4, 16 and, for element units, 64: a spare unit is a
+// predicated-off load and a +0.0 in the tree, not a byte of traffic).
+template <int MODE, bool PULL>
+int launch_rowwise(psg_table* t, bool vec, const RowwiseSrc& src, uint64_t m, float lr, hipStream_t st) {
+  const uint32_t upr = vec ? t->width / 4 : t->width;
+  uint32_t lg = 0;
+  while (lg < 6 && (1u << lg) < upr) ++lg;
+  const uint32_t need = (upr + 63) / 64;
+  const uint32_t gpb = (uint32_t)kBlock >> lg;
+  const unsigned grid = grid_for((m + gpb - 1) / gpb);
+  const RowwiseArgs a = {lr, t->ag_lr, t->ag_eps, (double)t->width};
+  auto go = [&](auto v, auto upl) {
+    k_rows_walk_rowwise<decltype(v)::value, decltype(upl)::value, MODE, PULL>
+        <<<grid, kBlock, 0, st>>>((float*)t->rows, t->accum, t->slots, src, m, upr, lg, a);
+  };
+  using std::integral_constant;
+  if (vec) {
+    if (need <= 1) go(std::true_type{}, integral_constant<int, 1>{});
+    else if (need <= 4) go(std::true_type{}, integral_constant<int, 4>{});
+    else go(std::true_type{}, integral_constant<int, 16>{});
+  } else {
+    if (need <= 1) go(std::false_type{}, integral_constant<int, 1>{});
+    else if (need <= 4) go(std::false_type{}, integral_constant<int, 4>{});
+    else if (need <= 16) go(std::false_type{}, integral_constant<int, 16>{});
+    else go(std::false_type{}, integral_constant<int, 64>{});
+  }
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+template <int MODE>
+int launch_rowwise(psg_table* t, bool pull, bool vec, const RowwiseSrc& src, uint64_t m, float lr, hipStream_t st) {
+  return pull ? launch_rowwise<MODE, true>(t, vec, src, m, lr, st) : launch_rowwise<MODE, false>(t, vec, src, m, lr, st);
+}
+
 // The body of the four request calls; `name` is the call's, for its messages.
 // opt: psg_table_update* (vals are gradients) instead of psg_table_handle*;
 // any: a list that is not strictly ascending is planned instead of rejected.
@@ -1972,6 +2296,14 @@ int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const u
   }
   if (opt) {
     const bool vec = optimize_vec(t, flags, (const float*)vals, (const float*)out);
+    if (t->adagrad) {  // one step per occurrence: the plan's unique rows, or the request's own
+      RowwiseSrc src = {};
+      src.seg = p ? p->seg : nullptr;
+      src.idx = p ? p->perm : nullptr;
+      src.grads = (const float*)vals;
+      src.out = (float*)out;
+      PSG_TRY(launch_rowwise<kRowwiseEach>(t, (flags & PSG_PULL) != 0, vec, src, p ? p->m : n, lr, st));
+    } else
     PSG_TRY(with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
       return launch_op<typename decltype(unit)::type>(t, flags, p, vals, out, n, upr, prm, st);
     }));
@@ -2208,6 +2540,16 @@ int launch_walk_pool(psg_table* t, const AnyPlan* p, const uint32_t* bags, const
 // vec: 16-B units (optimize_vec's condition for a Push, on every gradient array)
 int pooled_step(psg_table* t, bool vec, const AnyPlan* p, const uint32_t* bags, const float* grads, const Frames* f,
                 const PoolScale& sc, uint64_t n, float lr, int iteration, hipStream_t st) {
+  if (t->adagrad) {  // launch_walk_pool's choices, as one source
+    RowwiseSrc src = {};
+    src.seg = p ? p->seg : nullptr;
+    src.idx = (f || (p && !sc.weights)) ? p->perm : bags;
+    src.grads = grads;
+    src.w = sc.weights;
+    src.offsets = sc.weights ? nullptr : sc.offsets;
+    if (f) src.f = *f;
+    return launch_rowwise<kRowwiseSum, false>(t, vec, src, p ? p->m : n, lr, st);
+  }
   return with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
     return launch_walk_pool<typename decltype(unit)::type>(t, p, bags, grads, f, sc, n, upr, prm, st);
   });
@@ -2344,6 +2686,7 @@ int psg_table_destroy(psg_table* t) {
   if (t->keys) (void)hipFree(t->keys);
   if (t->slots) (void)hipFree(t->slots);
   if (t->mom) (void)hipFree(t->mom);
+  if (t->accum) (void)hipFree(t->accum);
   if (t->any_buf) (void)hipFree(t->any_buf);
   if (t->gate) (void)hipFree(t->gate);
   if (t->flags_host) (void)hipHostFree(t->flags_host);
@@ -2394,6 +2737,7 @@ int psg_table_set_adam(psg_table* t, double learning_rate, double beta1, double 
   PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_set_adam: null table");
   PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "psg_table_set_adam: the update is built for F32 tables");
   PSG_REQUIRE(!t->adam, PSG_ERR_INVALID, "psg_table_set_adam: the table already has Adam state");
+  PSG_REQUIRE(!t->adagrad, PSG_ERR_INVALID, "psg_table_set_adam: the table has Adagrad state");
   PSG_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1, PSG_ERR_INVALID,
               "psg_table_set_adam: beta1 %g / beta2 %g outside [0, 1)", beta1, beta2);
   PSG_REQUIRE(epsilon >= 0, PSG_ERR_INVALID, "psg_table_set_adam: epsilon %g below 0", epsilon);
@@ -2414,6 +2758,56 @@ int psg_table_set_adam(psg_table* t, double learning_rate, double beta1, double 
   t->beta1 = beta1;
   t->beta2 = beta2;
   t->eps = epsilon;
+  return PSG_OK;
+}
+
+int psg_table_set_adagrad(psg_table* t, double learning_rate, double epsilon, double initial_accumulator) {
+  const char* name = "psg_table_set_adagrad";
+  PSG_TRY(require_table(name, t));
+  PSG_TRY(require_f32(name, t));
+  PSG_REQUIRE(!t->adam && !t->adagrad, PSG_ERR_INVALID, "%s: the table already has %s state", name,
+              t->adam ? "Adam" : "Adagrad");
+  PSG_REQUIRE(std::isfinite(learning_rate), PSG_ERR_INVALID, "%s: learning_rate %g is not finite", name, learning_rate);
+  PSG_REQUIRE(std::isfinite(epsilon) && epsilon >= 0, PSG_ERR_INVALID, "%s: epsilon %g negative or not finite", name,
+              epsilon);
+  PSG_REQUIRE(std::isfinite(initial_accumulator) && initial_accumulator >= 0, PSG_ERR_INVALID,
+              "%s: initial_accumulator %g negative or not finite", name, initial_accumulator);
+  t->ag_init = initial_accumulator;
+  if (t->capacity) {
+    double* accum = nullptr;
+    PSG_HIP(hipMalloc((void**)&accum, t->capacity * sizeof(double)));
+    // on the null stream, waited for: done before the caller's streams use the accumulators
+    int rc = t->size ? fill_accum(t, accum, nullptr, t->size, nullptr) : (int)PSG_OK;
+    if (rc == PSG_OK) {
+      const hipError_t e = hipStreamSynchronize(nullptr);
+      if (e != hipSuccess) rc = hip_fail(e, name, __FILE__, __LINE__);
+    }
+    if (rc != PSG_OK) {
+      (void)hipFree(accum);
+      return rc;
+    }
+    t->accum = accum;
+  }
+  t->adagrad = 1;
+  t->ag_lr = learning_rate;
+  t->ag_eps = epsilon;
+  return PSG_OK;
+}
+
+int psg_table_get_adagrad(psg_table* t, int* has, double* params3) {
+  PSG_REQUIRE(t && has, PSG_ERR_INVALID, "psg_table_get_adagrad: null argument");
+  *has = t->adagrad;
+  if (params3) params3[0] = t->ag_lr, params3[1] = t->ag_eps, params3[2] = t->adagrad ? t->ag_init : 0.0;
+  return PSG_OK;
+}
+
+int psg_table_dump_accum(psg_table* t, double* acc_host) {
+  PSG_REQUIRE(t, PSG_ERR_INVALID, "psg_table_dump_accum: null table");
+  PSG_REQUIRE(t->adagrad, PSG_ERR_INVALID, "psg_table_dump_accum: the table has no Adagrad state");
+  if (t->size == 0) return PSG_OK;
+  PSG_REQUIRE(acc_host, PSG_ERR_INVALID, "psg_table_dump_accum: null argument");
+  PSG_HIP(hipDeviceSynchronize());
+  PSG_HIP(hipMemcpy(acc_host, t->accum, t->size * sizeof(double), hipMemcpyDeviceToHost));
   return PSG_OK;
 }
 
@@ -2499,6 +2893,16 @@ int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* cons
       if (f.out[j]) f.out[j] = moved_back(t, f.out[j], f.off[j]);
     }
   }
+  if (t->adagrad) {
+    RowwiseSrc src = {};
+    src.f = f;
+    if (p) {  // grads stays null: a position of the concatenation picks its frame
+      src.seg = p->seg, src.idx = p->perm;
+      PSG_TRY(launch_rowwise<kRowwiseSum>(t, pull, vec, src, p->m, lr, st));
+    } else {
+      PSG_TRY(launch_rowwise<kRowwiseSame>(t, pull, vec, src, n, lr, st));
+    }
+  } else
   PSG_TRY(with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
     using UNIT = typename decltype(unit)::type;
     return flags == PSG_PUSH ? launch_merged<UNIT, PSG_PUSH>(t, p, f, n, upr, prm, st)
@@ -2672,7 +3076,7 @@ int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* er
   PSG_TRY(read_count((const uint32_t*)counts.p + ntiles, &m, st));
   PSG_REQUIRE(m <= S, PSG_ERR_HIP, "%s: %llu survivors of %llu rows", name, (unsigned long long)m, (unsigned long long)S);
   if (m == S) return PSG_OK;  // no key of the list is present
-  DevBuf K2, R2, M2;
+  DevBuf K2, R2, M2, A2;
   uint64_t cap = 0;
   if (m) {
     cap = std::max<uint64_t>(m, 1024);
@@ -2681,14 +3085,16 @@ int psg_table_erase(psg_table* t, const uint64_t* keys, uint64_t n, uint64_t* er
     PSG_HIP(hipMalloc(&K2.p, cap * sizeof(uint64_t)));
     PSG_HIP(hipMalloc(&R2.p, cap * row_bytes));
     if (t->adam) PSG_HIP(hipMalloc(&M2.p, cap * mom_row_bytes(t)));
+    if (t->adagrad) PSG_HIP(hipMalloc(&A2.p, cap * sizeof(double)));
     compact_emit(S, (const uint32_t*)counts.p, alive, EmitSurvivor{t->keys, (uint64_t*)K2.p, (uint32_t*)from.p}, st);
     PSG_HIP(hipGetLastError());
     PSG_TRY(move_rows(t, true, t->rows, R2.p, (const uint32_t*)from.p, m, st));
     if (t->adam) PSG_TRY(launch_move<u32x4>(true, t->mom, M2.p, (const uint32_t*)from.p, m, t->width, st));
+    if (t->adagrad) PSG_TRY(launch_move<uint64_t>(true, t->accum, A2.p, (const uint32_t*)from.p, m, 1, st));
     PSG_HIP(hipStreamSynchronize(st));
   }
   // a table whose last key went keeps no arrays
-  publish_arrays(t, K2, R2, M2, m, cap);
+  publish_arrays(t, K2, R2, M2, A2, m, cap);
   if (erased_host) *erased_host = S - m;
   return PSG_OK;
 }

@@ -90,15 +90,41 @@ struct RowInit {
   }
 };
 
+// What the optimizer handles' SetAdagrad(epsilon, initial_accumulator) keeps until
+// the table is created: row-wise Adagrad (psg_table_set_adagrad) in place of SGD,
+// one f64 accumulator per row, with the handle's learning rate, widened.  Called
+// before the first request, like SetInit, and not on a handle built with use_adam.
+// A checkpoint file holds rows only: SaveModel warns, and a resumed run starts its
+// accumulators from initial_accumulator again.
+struct RowAdagrad {
+  bool set = false;
+  double eps = 1e-8, init = 0.0;
+  void Set(const char* who, psg_table* table, bool use_adam, double eps_, double init_) {
+    CHECK(!table) << who << "::SetAdagrad comes before the first request, SaveModel or LoadModel: the table exists";
+    CHECK(!use_adam) << who << "::SetAdagrad on a handle built with use_adam";
+    CHECK(!set) << who << "::SetAdagrad was called twice";
+    set = true, eps = eps_, init = init_;
+  }
+  void WarnOnSave(const char* who) const {
+    if (set)
+      LOG(WARNING) << who << "::SaveModel: the file holds rows only; the Adagrad accumulators are not saved and a "
+                   << "resumed run starts them from " << init << " again";
+  }
+};
+
 // The row handles' table, created on first use (a request, SaveModel or
 // LoadModel): [0, kMaxKey), no rows allocated; with_adam gives it the moments
-// of Adam(learning_rate), as LRServer.h:83-84 constructs it; init, where set,
-// its initializer.
+// of Adam(learning_rate), as LRServer.h:83-84 constructs it; adagrad, where set,
+// the accumulators of row-wise Adagrad(learning_rate); init, where set, its
+// initializer.
 inline psg_table* EnsureRowTable(psg_table** table, int dtype, uint32_t width, bool with_adam = false,
-                                 float learning_rate = 0.f, const RowInit* init = nullptr) {
+                                 float learning_rate = 0.f, const RowInit* init = nullptr,
+                                 const RowAdagrad* adagrad = nullptr) {
   if (*table) return *table;
   device::Check(psg_table_create(dtype, width, 0, kMaxKey, 0, table), "psg_table_create");
   if (with_adam) device::Check(psg_table_set_adam(*table, (double)learning_rate, 0.9, 0.999, 1e-8), "psg_table_set_adam");
+  if (adagrad && adagrad->set)
+    device::Check(psg_table_set_adagrad(*table, (double)learning_rate, adagrad->eps, adagrad->init), "psg_table_set_adagrad");
   if (init && init->set)
     device::Check(psg_table_set_init(*table, PSG_INIT_UNIFORM, init->seed, init->lo, init->hi), "psg_table_set_init");
   return *table;

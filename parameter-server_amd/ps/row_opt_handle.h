@@ -63,6 +63,7 @@ struct KVServerRowOptHandle {
     int iteration = 0;
     bool any_order = false;
     detail::RowInit init;
+    detail::RowAdagrad adagrad;
     ~State() {
       if (table) psg_table_destroy(table);
     }
@@ -137,6 +138,10 @@ struct KVServerRowOptHandle {
   int iteration() const { return state->iteration; }
   // New rows start from seeded uniform values in [lo, hi] (detail::RowInit, ps/row_handle.h)
   void SetInit(uint64_t seed, float lo, float hi) { state->init.Set("KVServerRowOptHandle", state->table, seed, lo, hi); }
+  // Row-wise Adagrad with the handle's learning rate in place of SGD (detail::RowAdagrad, ps/row_handle.h)
+  void SetAdagrad(double epsilon = 1e-8, double initial_accumulator = 0.0) {
+    state->adagrad.Set("KVServerRowOptHandle", state->table, state->use_adam, epsilon, initial_accumulator);
+  }
   // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
   size_t size() const { return detail::RowTableSize(state->table); }
 
@@ -146,12 +151,16 @@ struct KVServerRowOptHandle {
   // assigns the keys of this server's own range, SETS the iteration to the
   // file's and returns the rows loaded: call it once per saved shard, whatever
   // the number of servers that saved.
-  void SaveModel(const std::string& path) { SaveRowTable(Table(), state->iteration, path); }
+  void SaveModel(const std::string& path) {
+    state->adagrad.WarnOnSave("KVServerRowOptHandle");
+    SaveRowTable(Table(), state->iteration, path);
+  }
   int LoadModel(const std::string& path) { return detail::LoadOwnRows(Table(), path, &state->iteration); }
 
  private:
   psg_table* Table() {
-    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr, &state->init);
+    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr, &state->init,
+                                  &state->adagrad);
   }
 };
 

@@ -97,6 +97,7 @@ struct KVServerRowSyncHandle {
     int iteration = 0;
     std::vector<Held> held;
     detail::RowInit init;
+    detail::RowAdagrad adagrad;
     ~State() {
       if (table) psg_table_destroy(table);
     }
@@ -175,6 +176,10 @@ struct KVServerRowSyncHandle {
   int iteration() const { return state->iteration; }
   // New rows start from seeded uniform values in [lo, hi] (detail::RowInit, ps/row_handle.h)
   void SetInit(uint64_t seed, float lo, float hi) { state->init.Set("KVServerRowSyncHandle", state->table, seed, lo, hi); }
+  // Row-wise Adagrad with the handle's learning rate in place of SGD (detail::RowAdagrad, ps/row_handle.h)
+  void SetAdagrad(double epsilon = 1e-8, double initial_accumulator = 0.0) {
+    state->adagrad.Set("KVServerRowSyncHandle", state->table, state->use_adam, epsilon, initial_accumulator);
+  }
   // the rows the table holds now: a lookup leaves it as it is, an erase lowers it
   size_t size() const { return detail::RowTableSize(state->table); }
 
@@ -183,6 +188,7 @@ struct KVServerRowSyncHandle {
   // that is half gathered fails the CHECK.
   void SaveModel(const std::string& path) {
     CHECK(state->held.empty()) << "KVServerRowSyncHandle::SaveModel: " << state->held.size() << " Pushes of a round are held";
+    state->adagrad.WarnOnSave("KVServerRowSyncHandle");
     SaveRowTable(Table(), state->iteration, path);
   }
   int LoadModel(const std::string& path) {
@@ -192,7 +198,8 @@ struct KVServerRowSyncHandle {
 
  private:
   psg_table* Table() {
-    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr, &state->init);
+    return detail::EnsureRowTable(&state->table, PSG_F32, state->width, state->use_adam, state->lr, &state->init,
+                                  &state->adagrad);
   }
 
   // LRServer.h:163-178: the update on the merged gradients, then every held answer

@@ -57,6 +57,7 @@ EXPORTS = [
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
     "psg_table_lookup_pooled_weighted", "psg_table_update_pooled_weighted", "psg_table_update_pooled_merged",
     "psg_table_set_init", "psg_table_get_init", "psg_init_rows",
+    "psg_table_set_adagrad", "psg_table_get_adagrad", "psg_table_dump_accum",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
     "psg_pool_reduce_mean", "psg_pool_scale_mean",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
@@ -169,6 +170,9 @@ def lib() -> C.CDLL:
             "psg_table_update_any": ([vp, i32, vp, vp, vp, u64, f32, i32, vp], i32),
             "psg_table_update_merged": ([vp, i32, i32, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
             "psg_table_get_adam": ([vp, C.POINTER(i32), C.POINTER(f64)], i32),
+            "psg_table_set_adagrad": ([vp, f64, f64, f64], i32),
+            "psg_table_get_adagrad": ([vp, C.POINTER(i32), C.POINTER(f64)], i32),
+            "psg_table_dump_accum": ([vp, vp], i32),
             "psg_table_assign": ([vp, vp, vp, vp, vp, u64, vp], i32),
             "psg_table_export": ([vp, u64, u64, vp, vp, vp, vp, vp], i32),
             "psg_table_lookup": ([vp, vp, vp, vp, u64, vp], i32),
@@ -635,6 +639,24 @@ class Table:
         has, p = C.c_int(0), (C.c_double * 4)()
         _call("psg_table_get_adam", self.h, C.byref(has), p)
         return tuple(p) if has.value else None
+
+    def set_adagrad(self, lr: float, eps: float = 1e-8, initial_accumulator: float = 0.0) -> None:
+        """Row-wise Adagrad (psg_table_set_adagrad): one f64 accumulator per row,
+        initial_accumulator for every row present and inserted later; every update
+        call then takes its step in place of the SGD step."""
+        _call("psg_table_set_adagrad", self.h, lr, eps, initial_accumulator)
+
+    def adagrad(self):
+        """None, or the (lr, eps, initial_accumulator) set_adagrad got."""
+        has, p = C.c_int(0), (C.c_double * 3)()
+        _call("psg_table_get_adagrad", self.h, C.byref(has), p)
+        return tuple(p) if has.value else None
+
+    def dump_accum(self):
+        """The Adagrad accumulators, one per row, in key order."""
+        acc = np.empty(self.info().size, dtype=np.float64)
+        _call("psg_table_dump_accum", self.h, acc.ctypes.data_as(C.c_void_p))
+        return acc
 
     def assign(self, keys, rows, n: int, m=None, v=None, stream=None) -> None:
         """Set the rows of n ascending device keys to `rows` as bytes
