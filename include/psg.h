@@ -30,6 +30,8 @@
  *                    (no pooling in the reference)
  *   psg_table_lookup_pooled_weighted / _update_pooled_weighted
  *                    the same with a weight per id, or the bag's mean
+ *   psg_table_pooled_weight_grad
+ *                    the weighted bag's gradient with respect to its weights
  *   psg_table_update_pooled_merged
  *                    the sync-mode round over k frames, pooled or plain
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
@@ -890,8 +892,8 @@ int psg_table_update_pooled(psg_table* t, const uint64_t* keys, const uint64_t* 
  * psg_table_update_pooled's contract: per id the E rows of its occurrences are
  * summed from +0.0f in arrival order, one f32 add each, the optimizer steps
  * ONCE, an absent id is inserted once, an empty bag's gradient row is never
- * read, F32 tables only.  The gradient with respect to the weights is the
- * caller's.
+ * read, F32 tables only.  The gradient with respect to the weights is
+ * psg_table_pooled_weight_grad, below.
  * Refused before any device call, in this order: what the unweighted call
  * refuses with PSG_ERR_INVALID (a null table; null keys with n > 0; null
  * offsets or null out / grads with nb > 0; nb == 0 with n > 0); mode outside
@@ -912,6 +914,51 @@ int psg_table_lookup_pooled_weighted(psg_table* t, const uint64_t* keys, const u
 int psg_table_update_pooled_weighted(psg_table* t, const uint64_t* keys, const uint64_t* offsets,
                                      const float* weights, int mode, const float* grads, uint64_t n,
                                      uint64_t nb, float lr, int iteration, psg_stream stream);
+/* The other half of the weighted bag's backward: the gradient with respect to
+ * the WEIGHTS, dw[p] = <grads[bag(p)], row(keys[p])> for every position p of the
+ * id list.  keys, offsets, n and nb are psg_table_lookup_pooled's (ids in any
+ * order, repeats and empty bags allowed); grads holds nb * width f32 on the
+ * device, one gradient row per bag whatever the table's dtype; dw holds n f32 on
+ * the device, one per position of keys.  There is no weights argument: dw does
+ * not depend on the weights.  Every dtype (F32, F64, F16, BF16) and every width
+ * is served, and no row crosses the interface.
+ * Every result is bit for bit.  For position p in bag b, with W = width and P =
+ * W rounded up to a power of two:
+ *   x[c] = (double)row(keys[p])[c]           -- exact widening; an F64 row as it is
+ *   g[c] = (double)grads[b*W + c]
+ *   y[c] = g[c] * x[c]     for c < W          -- ONE f64 multiply, never fused
+ *   y[c] = -0.0            for W <= c < P
+ *   for h = P/2, P/4, ..., 1:  y[c] = y[c] + y[c + h]  for c < h   -- f64 adds, this tree and no other
+ *   dw[p] = (float)y[0]                       -- one round-to-nearest-even
+ * This is the row-wise Adagrad tree (psg_table_set_adagrad) with a product in
+ * the square's place.  The product of two significands of at most 24 bits fits
+ * f64's 53 and its exponent f64's range, so for F32, F16 and BF16 tables the
+ * multiply is exact and only the tree's adds round.  The padding is MINUS zero:
+ * a product can be -0.0 here (a square cannot), (-0.0) + (+0.0) is +0.0, and a
+ * row of -0.0 against positive gradients must give -0.0; y + (-0.0) is y for
+ * every y, both zeros included, and a subtree of padding stays -0.0, so padding
+ * the width, the lanes or the units changes no bit.
+ * An id the table does not hold gives dw[p] = +0.0f, and neither a row nor its
+ * gradient row is read for it: the forward's "adds nothing whatever its weight"
+ * (an infinite gradient makes no NaN there).  On a table with an initializer
+ * (psg_table_set_init) it takes the initial row of its key, as the pooled
+ * lookups do.  Nothing is ever inserted: size, capacity, keys, rows, moments,
+ * accumulators and the device pointers of psg_table_info are left as
+ * psg_table_lookup leaves them.  An empty bag's gradient row is never read.
+ * Refused before any device call, in this order: what psg_table_lookup_pooled
+ * refuses with PSG_ERR_INVALID, grads in out's place (a null table; null keys
+ * with n > 0; null offsets or null grads with nb > 0; nb == 0 with n > 0); null
+ * dw with n > 0; grads, then dw, not on a 4-B boundary (all PSG_ERR_INVALID).
+ * Then n or nb above 2^32 - 2 (PSG_ERR_RANGE).  nb == 0 is a no-op.  Found on
+ * the device as in the pooled lookups: bad offsets -> PSG_ERR_INVALID, a key
+ * out of range -> PSG_ERR_RANGE, both -> PSG_ERR_INVALID; dw is then not
+ * written.  Three kernels (offsets check, any-order resolve, the dot products
+ * behind the flags on the device) and ONE host synchronisation, at the end;
+ * request scratch grows with n, never with n * width.  Complete on return, as
+ * psg_table_lookup is. */
+int psg_table_pooled_weight_grad(psg_table* t, const uint64_t* keys, const uint64_t* offsets,
+                                 const float* grads, float* dw, uint64_t n, uint64_t nb,
+                                 psg_stream stream);
 /* One sync-mode round whose frames may be pooled: psg_table_update_merged's
  * Push with psg_table_update_pooled's gradient rows.  The five *_host arguments
  * are host arrays of k entries, 1 <= k <= 16; keys_host, offsets_host and

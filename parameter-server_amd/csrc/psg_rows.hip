@@ -88,6 +88,12 @@
 // a group of up to 64 lanes owns a unique row, sums the squares in a fixed tree
 // (in-lane adds, then a shuffle butterfly over the group) and steps the row.  A
 // follows its rows through insert, growth and erase as rows of one 8-B unit.
+//
+// The weighted bag's gradient with respect to its weights
+// (psg_table_pooled_weight_grad) is the pooled lookup's pipeline with
+// k_rows_pool_wgrad behind it: the row-wise groups and tree again, on the f64
+// products of a position's row and its bag's gradient row, the work cut by
+// position and not by bag.  It writes n floats and nothing to the table.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1716,6 +1722,211 @@ __global__ __launch_bounds__(256) void k_rows_walk_rowwise(float* __restrict__ R
 #pragma clang attribute pop
 #endif
 
+// ---- the gradient of a weighted bag with respect to its weights ---------------------
+// (psg_table_pooled_weight_grad)  dw[p] = <grads[bag(p)], row(keys[p])> for every
+// position p of the id list, in the tree include/psg.h defines:
+//   y[c] = (double)grads[b][c] * (double)row[c], -0.0 from width up to P (a power of two)
+//   for h = P/2 .. 1:  y[c] += y[c + h] for c < h;   dw[p] = (float)y[0]
+// — the row-wise Adagrad tree with a product in the square's place, and the same
+// lanes: a GROUP of G = 2^lg lanes (G <= 64, inside one wave) holds a row, lane l
+// units l, l + G, ... of it, UPL of them at most.  A unit is 16 B of the row (VEC:
+// E = 4 f32, 2 f64 or 8 half columns) or one element.  By the stride of its levels:
+//   h >= G units   in-lane adds between the lane's own units, depth first (sq_tree);
+//   G > h >= 1     the butterfly over the group, y += shfl_xor(y, h), every lane
+//                  ending with the defined bits;
+//   h < E columns  the unit's own levels (unit_tree): (y0 + y2) + (y1 + y3) for four.
+// A spare column, unit, lane or level holds -0.0: y + -0.0 is y for EVERY y, -0.0
+// included (+0.0 would turn a sum of -0.0 terms into +0.0), so the bits do not
+// depend on G, UPL, E or the unit.
+// The work is cut by POSITION: a group owns kWgradChunk consecutive positions,
+// whatever bags they fall in, so one bag of a million ids and a million bags of
+// one id are the same load.  The chunk's first bag is the last offset <= its first
+// position (a search over `offsets`, which skips empty bags by itself); from
+// there the walk steps to the next bag when a position passes the bag's end.  The
+// bag's gradient row lives in the group's registers as f32 and is loaded when a
+// present position finds another bag's row there: once per (chunk, bag), never
+// for an empty bag or one whose ids are all absent.  The chain is slot -> row
+// units -> products: the slot is loaded two positions ahead and, while two rows
+// fit the registers (kAhead), the row's units one position ahead.  After the
+// butterfly every lane holds dw[p]; lane (p - chunk start) % G keeps it and the
+// group stores G consecutive floats at a time.  One writer per word, no atomics,
+// no LDS, no scratch.  An absent slot stores +0.0f and reads nothing or, INIT
+// (a table with an initializer), makes its units from the key as
+// k_rows_pool_init does.  Algorithmic bytes per position: key 8 + slot 8 + the
+// row + 4, and a gradient row per (chunk, bag).
+constexpr uint32_t kWgradChunk = 64;  // positions per group and turn: a multiple of every G
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+// the levels inside a unit of E columns: (the even columns) + (the odd ones), each the same again
+template <int S, int O, int E>
+__device__ __forceinline__ double unit_tree(const double (&y)[E]) {
+  if constexpr (S >= E) return y[O];
+  else return unit_tree<2 * S, O, E>(y) + unit_tree<2 * S, O + S, E>(y);
+}
+
+// f(K), f(K + 1), ... f(N - 1), every index a constant
+template <int K, int N, typename F>
+__device__ __forceinline__ void each_unit(const F& f) {
+  if constexpr (K < N) {
+    f(K);
+    each_unit<K + 1, N>(f);
+  }
+}
+
+template <int DT, bool VEC, int UPL, bool INIT>
+__global__ __launch_bounds__(256) void k_rows_pool_wgrad(const typename PoolAcc<DT, VEC>::U* __restrict__ R,
+                                                         const uint32_t* __restrict__ slots,
+                                                         const uint64_t* __restrict__ q,
+                                                         const uint64_t* __restrict__ offsets,
+                                                         const float* __restrict__ grads, float* __restrict__ dw,
+                                                         uint64_t n, uint64_t nb, uint32_t upr, uint32_t lg,
+                                                         const int* __restrict__ gate, InitSpec spec) {
+  using ACC = PoolAcc<DT, VEC>;
+  using U = typename ACC::U;
+  constexpr int E = VEC ? Elem<DT>::kVec : 1;
+  // the next position's units are loaded before the current ones are used while both fit
+  constexpr bool kAhead = UPL * (int)sizeof(U) <= 64;
+  if (gate[R_RANGE] | gate[R_OFFSETS]) return;
+  // a lane holds more than one unit only where the row has more than 64: then G is 64, a
+  // constant, and so are the units' distances (folded into the loads, not kept in registers)
+  const uint32_t G = UPL > 1 ? 64u : 1u << lg;
+  const uint32_t l = threadIdx.x & (G - 1);
+  const uint32_t gpb = kBlock / G;  // groups per block
+  const uint32_t width = upr * E;
+
+  // this lane's units of the row in `slot` (absent and INIT: of key q[p]'s initial row);
+  // both lambdas are inlined whatever their size: a call would put the registers in memory
+  auto load_row = [&](U (&x)[UPL], uint32_t slot, uint32_t p) __attribute__((always_inline)) {
+    [[maybe_unused]] uint64_t key = 0;
+    if constexpr (INIT)
+      if (slot == kAbsent) key = q[p];
+    // written out unit by unit (each_unit), not as a loop to unroll: 64 units of Philox
+    // rounds are past the size a loop is unrolled to, and a loop left over indexes x in memory
+    each_unit<0, UPL>([&](int k) __attribute__((always_inline)) {
+      const uint32_t c = l + (uint32_t)k * G;
+      x[k] = U{};
+      if (c >= upr) return;
+      if (slot != kAbsent) x[k] = R[(uint64_t)slot * upr + c];
+      else if constexpr (INIT) {
+        const auto made = InitUnit<DT, VEC>::make(key, c, spec);
+        x[k] = __builtin_bit_cast(U, made);
+        if constexpr (!kAhead) {
+          // a wide row: the next unit's Philox rounds wait for this unit (the key passes through
+          // an empty asm that reads it), so UPL blocks are never alive side by side
+          uint32_t tie;
+          if constexpr (VEC) tie = made[0];
+          else tie = (uint32_t)made;
+          asm volatile("" : "+v"(key) : "v"(tie));
+        }
+      }
+    });
+  };
+  // this lane's units of bag b's gradient row: E floats a unit, in loads of at most 16 B
+  auto load_grad = [&](float (&g)[UPL][E], uint32_t b) __attribute__((always_inline)) {
+    const float* const row = grads + (uint64_t)b * width;
+#pragma unroll
+    for (int k = 0; k < UPL; ++k) {
+      const uint32_t c = l + (uint32_t)k * G;
+      const bool in = c < upr;
+      if constexpr (E == 1) {
+        g[k][0] = in ? row[c] : 0.0f;
+      } else if constexpr (E == 2) {
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        f32x2 v = {};
+        if (in) v = reinterpret_cast<const f32x2*>(row)[c];
+        g[k][0] = v[0], g[k][1] = v[1];
+      } else {
+#pragma unroll
+        for (int j = 0; j < E / 4; ++j) {
+          f32x4 v = {};
+          if (in) v = reinterpret_cast<const f32x4*>(row)[(uint64_t)c * (E / 4) + j];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) g[k][4 * j + e] = v[e];
+        }
+      }
+    }
+  };
+
+  const uint64_t nchunks = (n + kWgradChunk - 1) / kWgradChunk;
+  const uint64_t stride = (uint64_t)gridDim.x * gpb;
+  for (uint64_t ch = (uint64_t)blockIdx.x * gpb + (threadIdx.x >> lg); ch < nchunks; ch += stride) {
+    // positions and bags as 32-bit words (n, nb <= 2^32 - 2: checked), so p + 2 and b + 1 do not wrap
+    const uint32_t c0 = (uint32_t)(ch * kWgradChunk);
+    const uint32_t c1 = (uint32_t)((ch + 1) * kWgradChunk < n ? (ch + 1) * kWgradChunk : n);
+    uint32_t s0 = slots[c0];
+    uint32_t s1 = c0 + 1 < c1 ? slots[c0 + 1] : kAbsent;
+    [[maybe_unused]] U x[UPL];
+    if constexpr (kAhead) load_row(x, s0, c0);
+    // the bag of c0: the last b with offsets[b] <= c0 (offsets[0] = 0 and offsets[nb]
+    // = n > c0 are checked, so b < nb and offsets[b + 1] > c0: the bag is not empty)
+    uint32_t b = 0;
+    for (uint32_t hi = (uint32_t)nb; hi - b > 1;) {  // offsets[b] <= c0 < offsets[hi]
+      const uint32_t mid = b + ((hi - b) >> 1);
+      if (offsets[mid] <= c0) b = mid;
+      else hi = mid;
+    }
+    uint32_t be = (uint32_t)offsets[b + 1];
+    uint32_t gb = kAbsent;  // the bag whose gradient row is in g: none yet (b < nb <= 2^32 - 2)
+    float g[UPL][E];
+    float keep = 0.0f;
+    for (uint32_t p = c0; p < c1; ++p) {
+      const uint32_t s2 = p + 2 < c1 ? slots[p + 2] : kAbsent;
+      [[maybe_unused]] U xn[UPL] = {};
+      if constexpr (kAhead)
+        if (p + 1 < c1) load_row(xn, s1, p + 1);
+      while (p >= be) be = (uint32_t)offsets[++b + 1];  // ends: offsets[nb] = n > p
+      float r = 0.0f;                         // an absent id of a table without an initializer
+      if (INIT || s0 != kAbsent) {
+        if (gb != b) load_grad(g, b), gb = b;
+        if constexpr (!kAhead) load_row(x, s0, p);
+        {
+          auto prod = [&](int k, double y[E]) {
+            const bool in = l + (uint32_t)k * G < upr;
+            const typename ACC::A xa = ACC::widen(x[k]);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+              double xe;
+              if constexpr (VEC) xe = (double)xa[e];
+              else xe = (double)xa;
+              float ge = g[k][e];
+              // wide rows: the gradient stays f32 in its registers and is widened here, at
+              // every use, not once per bag into twice the registers
+              if constexpr (UPL * E > 16) asm volatile("" : "+v"(ge));
+              const double t = (double)ge * xe;
+              y[e] = in ? t : -0.0;
+            }
+          };
+          double y[E];
+          sq_tree<1, 0, UPL, E>(prod, y);
+#pragma unroll
+          for (uint32_t d = 32; d >= 1; d >>= 1) {
+            if (d >= G) continue;
+#pragma unroll
+            for (int e = 0; e < E; ++e) y[e] = y[e] + __shfl_xor(y[e], (int)d, 64);
+          }
+          r = (float)unit_tree<1, 0, E>(y);
+        }
+      }
+      const uint32_t j = p - c0;
+      if ((j & (G - 1)) == l) keep = r;
+      if (((j + 1) & (G - 1)) == 0 || p + 1 == c1) {  // G results, or the chunk's tail
+        const uint32_t at = p - (j & (G - 1)) + l;
+        if (at <= p) dw[at] = keep;
+      }
+      s0 = s1, s1 = s2;
+      if constexpr (kAhead) {
+#pragma unroll
+        for (int k = 0; k < UPL; ++k) x[k] = xn[k];
+      }
+    }
+  }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 // A[to[j]] (to null: A[j]) = value for j < n: the accumulators of new rows
 __global__ __launch_bounds__(256) void k_accum_fill(double* __restrict__ A, const uint32_t* __restrict__ to, uint64_t n,
                                                     double value) {
@@ -2495,6 +2706,71 @@ int lookup_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
   return require_in_range(t);
 }
 
+// k_rows_pool_wgrad over the list's n positions: G and UPL chosen as launch_rowwise
+// chooses them (G = the row's units rounded up to a power of two, 64 at most; UPL
+// the units a lane then holds, rounded up to the next instantiation: 1, 4, 16, then
+// 32 for F64's 16-B units and 64 for element units), a group per chunk.
+template <int DT, bool VEC, bool INIT>
+int launch_wgrad(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads, float* dw, uint64_t n,
+                 uint64_t nb, hipStream_t st) {
+  using U = typename PoolAcc<DT, VEC>::U;
+  const uint32_t upr = VEC ? t->width / Elem<DT>::kVec : t->width;
+  uint32_t lg = 0;
+  while (lg < 6 && (1u << lg) < upr) ++lg;
+  const uint32_t need = (upr + 63) / 64;
+  const uint32_t gpb = (uint32_t)kBlock >> lg;
+  const uint64_t nchunks = (n + kWgradChunk - 1) / kWgradChunk;
+  const unsigned grid = grid_for((nchunks + gpb - 1) / gpb);
+  const InitSpec spec = INIT ? init_spec(t) : InitSpec{};
+  auto go = [&](auto upl) {
+    k_rows_pool_wgrad<DT, VEC, decltype(upl)::value, INIT>
+        <<<grid, kBlock, 0, st>>>((const U*)t->rows, t->slots, keys, offsets, grads, dw, n, nb, upr, lg, t->gate, spec);
+  };
+  using std::integral_constant;
+  constexpr int kWidest = !VEC ? 64 : DT == PSG_F64 ? 32 : 16;  // 4096 columns in 64 lanes
+  if (need <= 1) go(integral_constant<int, 1>{});
+  else if (need <= 4) go(integral_constant<int, 4>{});
+  else if (need <= 16) go(integral_constant<int, 16>{});
+  else go(integral_constant<int, kWidest>{});
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+
+// The body of psg_table_pooled_weight_grad: the pooled lookup's pipeline (offsets
+// check, any-order resolve, the gated kernel, one synchronisation) with
+// k_rows_pool_wgrad in k_rows_pool's place.  Request scratch: the n slots.
+int pooled_weight_grad(const char* name, psg_table* t, const uint64_t* keys, const uint64_t* offsets,
+                       const float* grads, float* dw, uint64_t n, uint64_t nb, psg_stream stream) {
+  PSG_TRY(pooled_args(name, t, keys, offsets, grads, "grads", n, nb));
+  PSG_REQUIRE(dw || n == 0, PSG_ERR_INVALID, "%s: null dw", name);
+  PSG_REQUIRE((reinterpret_cast<uintptr_t>(grads) & 3u) == 0, PSG_ERR_INVALID, "%s: grads not on a 4-B boundary", name);
+  PSG_REQUIRE((reinterpret_cast<uintptr_t>(dw) & 3u) == 0, PSG_ERR_INVALID, "%s: dw not on a 4-B boundary", name);
+  PSG_TRY(require_count(name, n));
+  PSG_TRY(require_count(name, nb, "bags"));
+  if (nb == 0) return PSG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  PSG_TRY(gate_begin(t, n, st));
+  PSG_TRY(launch_offsets_check(offsets, n, nb, t->gate, st));
+  if (n) {
+    PSG_TRY(launch_resolve(t, keys, n, t->gate, false, st));
+    // 16-B units: rows of a multiple of 16 B (the table's own rows start on 16 B) and every gradient row on 16 B
+    const bool vec = ((uint64_t)t->width * t->esize) % 16 == 0 && aligned16(grads);
+    PSG_TRY(with_dtype(t->dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (has_init(t)) {
+        if (vec) return launch_wgrad<DT, true, true>(t, keys, offsets, grads, dw, n, nb, st);
+        return launch_wgrad<DT, false, true>(t, keys, offsets, grads, dw, n, nb, st);
+      }
+      if (vec) return launch_wgrad<DT, true, false>(t, keys, offsets, grads, dw, n, nb, st);
+      return launch_wgrad<DT, false, false>(t, keys, offsets, grads, dw, n, nb, st);
+    }));
+  }
+  // the one synchronisation: keys, offsets and grads no longer read, dw in memory, the flags on the host
+  PSG_TRY(gate_end(t, st));
+  PSG_TRY(require_offsets(t, name, n));
+  return require_in_range(t);
+}
+
 // The pooled walk for one unit type and one source of gradient rows (src:
 // OneArray, WeightedArray, MeanArray or, always with a plan, FrameArrays): over
 // the plan's unique rows with bags[p] the gradient row of sorted position p, or
@@ -3121,6 +3397,11 @@ int psg_table_update_pooled_weighted(psg_table* t, const uint64_t* keys, const u
                                      psg_stream stream) {
   return update_pooled("psg_table_update_pooled_weighted", t, keys, offsets, weights, mode, grads, n, nb, lr, iteration,
                        stream, nullptr);
+}
+
+int psg_table_pooled_weight_grad(psg_table* t, const uint64_t* keys, const uint64_t* offsets, const float* grads,
+                                 float* dw, uint64_t n, uint64_t nb, psg_stream stream) {
+  return pooled_weight_grad("psg_table_pooled_weight_grad", t, keys, offsets, grads, dw, n, nb, stream);
 }
 
 // ---- the round of pooled and plain frames ------------------------------------------

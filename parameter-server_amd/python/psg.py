@@ -56,6 +56,7 @@ EXPORTS = [
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
     "psg_table_lookup_pooled_weighted", "psg_table_update_pooled_weighted", "psg_table_update_pooled_merged",
+    "psg_table_pooled_weight_grad",
     "psg_table_set_init", "psg_table_get_init", "psg_init_rows",
     "psg_table_set_adagrad", "psg_table_get_adagrad", "psg_table_dump_accum",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
@@ -181,6 +182,7 @@ def lib() -> C.CDLL:
             "psg_table_update_pooled": ([vp, vp, vp, vp, u64, u64, f32, i32, vp], i32),
             "psg_table_lookup_pooled_weighted": ([vp, vp, vp, vp, i32, vp, u64, u64, vp], i32),
             "psg_table_update_pooled_weighted": ([vp, vp, vp, vp, i32, vp, u64, u64, f32, i32, vp], i32),
+            "psg_table_pooled_weight_grad": ([vp, vp, vp, vp, vp, u64, u64, vp], i32),
             "psg_table_update_pooled_merged": ([vp, i32, vp, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
             "psg_table_set_init": ([vp, i32, u64, f32, f32], i32),
             "psg_table_get_init": ([vp, C.POINTER(i32), C.POINTER(u64), C.POINTER(f32), C.POINTER(f32)], i32),
@@ -711,6 +713,15 @@ class Table:
         bag's length (POOL_MEAN, weights None); then as update_pooled."""
         _call("psg_table_update_pooled_weighted", self.h, _ptr(keys), _ptr(offsets), _ptr(weights), mode, _ptr(grads),
               n, nb, lr, iteration, _s(stream))
+
+    def pooled_weight_grad(self, keys, offsets, grads, dw, n: int, nb: int, stream=None) -> None:
+        """The weighted bag's gradient with respect to its weights
+        (psg_table_pooled_weight_grad): dw[p] = the dot product of the gradient row
+        of p's bag (grads: nb rows of device float32) and the row of keys[p], n
+        device float32; an absent id gives +0 (or its initial row's product) and
+        nothing is inserted."""
+        _call("psg_table_pooled_weight_grad", self.h, _ptr(keys), _ptr(offsets), _ptr(grads), _ptr(dw), n, nb,
+              _s(stream))
 
     def update_pooled_merged(self, frames, ns, nbs, lr: float, iteration: int, stream=None) -> int:
         """One sync-mode round whose frames may be pooled
