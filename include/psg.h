@@ -658,6 +658,52 @@ int psg_table_get_adagrad(psg_table* t, int* has, double* params3);
  * PSG_ERR_INVALID on a table without Adagrad state.  Synchronous. */
 int psg_table_dump_accum(psg_table* t, double* acc_host);
 
+/* Give an F16 or BF16 table the row-wise Adagrad state of psg_table_set_adagrad:
+ * the same A[capacity] f64 accumulators, following their rows in the same way, and
+ * psg_table_get_adagrad / psg_table_dump_accum as they stand.  Every update call
+ * then takes such a table: grads stay const float*, and a PSG_PULL reply stays
+ * float*, the stored 16-bit row widened (exact).  A half table WITHOUT this state
+ * is refused by every update call with PSG_ERR_UNSUPPORTED, as before.
+ * The step: s[c], g[c], the tree, A, step and
+ *   x = (double)row[c] - step * g[c]
+ * are word for word those of psg_table_set_adagrad, row[c] being the stored half
+ * widened; the rows' values never enter A, so the accumulators equal those of an
+ * F32 table fed the same gradients.  Then v = (float)x, and the stored element is
+ * round16(v, r):
+ *   PSG_ROUND_NEAREST     the correctly rounded conversion of v to the table's dtype,
+ *                         ties to even; a NaN is stored as 0x7E00 (F16) / 0x7FC0 (BF16);
+ *   PSG_ROUND_STOCHASTIC  v not finite: the same.  v finite, r a 16-bit word:
+ *     q  = the dtype's spacing at |v|, a power of two (the subnormal range: the
+ *          smallest spacing, 2^-24 for F16 and 2^-133 for BF16)
+ *     t  = |v| / q (exact);  n = floor(t);  k = floor((t - n) * 65536)
+ *     up = (k + r) >> 16                                  -- 0 or 1
+ *     the result is sign(v) * (n + up) * q; a magnitude of 2^(emax + 1) or more, of
+ *     the result or of |v| itself (F16: 2^16), is +-inf; the sign bit of v is kept,
+ *     zeros included.  So v moves up with probability k / 65536 over uniform r and
+ *     a representable v (k == 0) never moves.  For BF16 this is "add r to the low
+ *     16 bits of v's f32 pattern and drop them".
+ * The word r of column c: b = c / 8, e = c % 8, and r is 16-bit half e (the low
+ * half of word 0 first) of
+ *   Philox4x32-10(counter = {key lo, key hi, A lo ^ A hi, b}, key = {seed lo, seed hi})
+ * where A is the bit pattern of the row's accumulator BEFORE this step.  A changes
+ * with every step whose gradient row is not all zero (and a column whose gradient
+ * is zero has x == row, stored unchanged whatever r is); in psg_table_update /
+ * _update_any it advances per occurrence, so every occurrence of a repeated id has
+ * words of its own.  Nothing else enters: not the slot, the number of servers, the
+ * call's `iteration` (checked as ever, not used) or a restart.  Once A is so large
+ * that a step no longer changes its bits the words repeat; that step is then below
+ * f64's resolution of A.
+ * Refused before any device call, in this order: a null table -> PSG_ERR_INVALID; a
+ * table that is neither F16 nor BF16 -> PSG_ERR_UNSUPPORTED; then, PSG_ERR_INVALID,
+ * psg_table_set_adagrad's four (state already there; learning_rate; epsilon;
+ * initial_accumulator) and a `rounding` that is neither of the two. */
+enum { PSG_ROUND_NEAREST = 0, PSG_ROUND_STOCHASTIC = 1 };
+int psg_table_set_adagrad_half(psg_table* t, double learning_rate, double epsilon,
+                               double initial_accumulator, int rounding, uint64_t seed);
+/* The rounding mode and seed psg_table_set_adagrad_half got (zeros without it).
+ * Host only. */
+int psg_table_get_rounding(psg_table* t, int* rounding, uint64_t* seed);
+
 /* What a NEW row starts from.  The reference's store[key] value-initialises to
  * zero (src/ps/KVApp.h:446-454), and so does a table by default; a model that
  * multiplies two looked-up rows never leaves the origin from there, so a table

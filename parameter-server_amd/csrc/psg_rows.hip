@@ -88,6 +88,10 @@
 // a group of up to 64 lanes owns a unique row, sums the squares in a fixed tree
 // (in-lane adds, then a shuffle butterfly over the group) and steps the row.  A
 // follows its rows through insert, growth and erase as rows of one 8-B unit.
+// An F16 / BF16 table takes the same state (psg_table_set_adagrad_half) and forks
+// to k_rows_walk_rowwise_half: the same groups and tree on units of 16 B of the
+// row, eight columns against 32 B of f32 gradient, and a rounding stage, to
+// nearest or stochastic by counter-based Philox words, in front of the store.
 //
 // The weighted bag's gradient with respect to its weights
 // (psg_table_pooled_weight_grad) is the pooled lookup's pipeline with
@@ -125,6 +129,10 @@ struct psg_table {
   int adagrad;
   double ag_lr, ag_eps, ag_init;
   double* accum;
+  // an F16 / BF16 table's Adagrad state (psg_table_set_adagrad_half) is the same, and
+  // how its step rounds: PSG_ROUND_*, and the seed of the stochastic words
+  int ag_round;
+  uint64_t ag_seed;
   // scratch of the order-preserving requests (psg_table_*_any): the sort's
   // buffers, perm, U and seg carved from one block grown on demand
   void* any_buf;
@@ -1927,6 +1935,356 @@ __global__ __launch_bounds__(256) void k_rows_pool_wgrad(const typename PoolAcc<
 #pragma clang attribute pop
 #endif
 
+// ---- row-wise Adagrad on 16-bit rows (psg_table_set_adagrad_half) -------------------
+// The step of k_rows_walk_rowwise on an F16 / BF16 row from f32 gradients, ending in
+// round16 (include/psg.h): x = (double)row[c] - step * g[c], v = (float)x, and the
+// stored half is v rounded to nearest even or, PSG_ROUND_STOCHASTIC, up or down by
+// a 16-bit word r of Philox4x32-10 on (key, A before the step, c / 8) under the
+// table's seed.  Groups, tree, modes and sources are the F32 kernel's: a group of
+// G = 2^lg lanes of one wave owns a unique row, lane l units l, l + G, ..., UPL of
+// them; no LDS staging, no atomics, one writer per row.  What differs is the unit:
+// VEC is 16 B of the ROW, eight columns, against 32 B of gradient (two f32x4
+// loads) and, when pulled, 32 B of reply; else one 2-B element.  So a lane's tree
+// has eight columns a unit, and its levels by stride are
+//   h >= 8G columns   in-lane, between the lane's units (sq_tree);
+//   8G > h >= 8       the butterfly, y[e] += shfl_xor(y[e], h / 8) per column e;
+//   h = 4, 2, 1       inside the unit (unit_tree<., ., 8>).
+// Spare columns, units and lanes hold +0.0, as there.  The row stays in its
+// registers as it is stored (four words a unit) and is widened at the step.
+// A unit IS one Philox block (b = c / 8 is the unit's index): its counter needs
+// the key and A-before, both loaded by the group's lane 0 beside the row and
+// broadcast, so the ten rounds of a lane's UPL blocks stand in front of the
+// tree, between the gradient loads and their first use.  An element unit makes
+// its block at the rounding and keeps one word of it (UPL of 64: the blocks of
+// a lane never live side by side).  PSG_ROUND_NEAREST computes no block.
+// No packed f32 arithmetic in the kernel and what it inlines, as in k_rows_walk_rowwise.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+struct HalfRound {
+  const uint64_t* K;  // the table's keys in slot order
+  uint32_t k0, k1;    // the seed's words
+  int stochastic;
+};
+
+// One 16-bit element as the low half of a word: widen is exact; nearest is the
+// correctly rounded conversion, ties to even, a NaN the format's 0x7E00 / 0x7FC0;
+// stochastic is round16 of the header on the f32 bits (a value that is not
+// finite: nearest).
+template <int DT> struct Half16;
+template <> struct Half16<PSG_BF16> {
+  __device__ static __forceinline__ float widen(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
+  __device__ static __forceinline__ uint32_t nearest(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+  }
+  // the low 16 bits of the pattern are (t - n) * 65536 in every binade, the f32
+  // subnormals included (BF16 has f32's exponents); the carry runs up to inf
+  __device__ static __forceinline__ uint32_t stochastic(float v, uint32_t r) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    if ((u & 0x7f800000u) == 0x7f800000u) return nearest(v);
+    return (u + r) >> 16;
+  }
+};
+template <> struct Half16<PSG_F16> {
+  __device__ static __forceinline__ float widen(uint32_t h) {
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
+  }
+  __device__ static __forceinline__ uint32_t nearest(float v) {
+    if ((__builtin_bit_cast(uint32_t, v) & 0x7fffffffu) > 0x7f800000u) return 0x7e00u;
+    return __builtin_bit_cast(uint16_t, (_Float16)v);
+  }
+  __device__ static __forceinline__ uint32_t stochastic(float v, uint32_t r) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    const uint32_t a = u & 0x7fffffffu, e = a >> 23;
+    if (e == 255u) return nearest(v);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    if (e >= 143u) return sign | 0x7c00u;  // |v| >= 2^16
+    // an F16 normal: 13 bits fall away, (low13 * 8 + r) >> 16 == (low13 + (r >> 3)) >> 13,
+    // and the carry runs through the mantissa into the exponent, up to inf
+    if (e >= 113u) return sign | (((a + (r >> 3)) >> 13) - 0x1c000u);
+    // below 2^-14 the spacing is 2^-24: T = floor(|v| * 2^40) = n * 65536 + k from the
+    // f32 fields (|v| = mant * 2^(e - 150), e = 1 for an f32 subnormal), T < 2^26
+    const uint32_t mant = e ? (a & 0x7fffffu) | 0x800000u : a;
+    const uint32_t ee = e ? e : 1u;
+    const uint32_t down = 110u - ee < 31u ? 110u - ee : 31u;  // mant < 2^24: 31 leaves 0
+    const uint32_t T = ee >= 110u ? mant << (ee - 110u) : mant >> down;
+    return sign | ((T + r) >> 16);
+  }
+};
+
+template <int DT, bool VEC, int UPL, int MODE, bool PULL>
+__global__ __launch_bounds__(256) void k_rows_walk_rowwise_half(uint16_t* __restrict__ R, double* __restrict__ A,
+                                                                const uint32_t* __restrict__ slots, RowwiseSrc src,
+                                                                uint64_t m, uint32_t upr, uint32_t lg, RowwiseArgs a,
+                                                                HalfRound hr) {
+  using H = Half16<DT>;
+  constexpr int E = VEC ? 8 : 1;
+  constexpr int W = VEC ? 4 : 1;  // the words a unit of the row takes in registers
+  // the next occurrence's units are loaded before the current one is used while both fit
+  constexpr bool kAhead = UPL * E <= 16;
+  __shared__ uint64_t vals_at[kMaxFrames], out_at[kMaxFrames];
+  if (threadIdx.x < kMaxFrames) vals_at[threadIdx.x] = (uint64_t)src.f.vals[threadIdx.x];
+  else if (threadIdx.x < 2 * kMaxFrames) out_at[threadIdx.x - kMaxFrames] = (uint64_t)src.f.out[threadIdx.x - kMaxFrames];
+  __syncthreads();
+  const uint32_t G = 1u << lg;
+  const uint32_t l = threadIdx.x & (G - 1);
+  const uint32_t head = (threadIdx.x & 63u) & ~(G - 1);  // the group's lane 0 in its wave
+  const uint32_t gpb = kBlock >> lg;                     // groups, and rows at a time, per block
+  const uint32_t width = upr * E;
+  const int pool = src.w ? kPoolWeighted : src.offsets ? kPoolMean : kPoolSum;
+
+  // this lane's units of a gradient row: E floats a unit, two 16-B loads for eight
+  auto load = [&](float (&x)[UPL][E], const float* row) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < UPL; ++k) {
+      const uint32_t c = l + (uint32_t)k * G;
+      if constexpr (VEC) {
+        f32x4 v0 = {}, v1 = {};
+        if (c < upr) {
+          v0 = reinterpret_cast<const f32x4*>(row)[2 * c];
+          v1 = reinterpret_cast<const f32x4*>(row)[2 * c + 1];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[k][e] = v0[e], x[k][4 + e] = v1[e];
+      } else {
+        x[k][0] = c < upr ? row[c] : 0.0f;
+      }
+    }
+  };
+  // this lane's units of the row, as stored: element e of a unit is half e & 1 of word e >> 1
+  auto load_row = [&](uint32_t (&q)[UPL][W], const uint16_t* row) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < UPL; ++k) {
+      const uint32_t c = l + (uint32_t)k * G;
+      if constexpr (VEC) {
+        u32x4 v = {};
+        if (c < upr) v = reinterpret_cast<const u32x4*>(row)[c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[k][j] = v[j];
+      } else {
+        q[k][0] = c < upr ? row[c] : 0u;
+      }
+    }
+  };
+  auto store_row = [&](const uint32_t (&q)[UPL][W], uint16_t* row) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < UPL; ++k) {
+      const uint32_t c = l + (uint32_t)k * G;
+      if (c >= upr) continue;
+      if constexpr (VEC) reinterpret_cast<u32x4*>(row)[c] = u32x4{q[k][0], q[k][1], q[k][2], q[k][3]};
+      else row[c] = (uint16_t)q[k][0];
+    }
+  };
+  auto half_of = [](const uint32_t (&q)[W], int e) -> uint32_t {
+    if constexpr (VEC) return (e & 1) ? q[e >> 1] >> 16 : q[e >> 1] & 0xffffu;
+    else return q[0];
+  };
+  // a reply: the row as it is stored, widened
+  auto store_reply = [&](const uint32_t (&q)[UPL][W], float* row) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < UPL; ++k) {
+      const uint32_t c = l + (uint32_t)k * G;
+      if (c >= upr) continue;
+      if constexpr (VEC) {
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = H::widen(half_of(q[k], e));
+        reinterpret_cast<f32x4*>(row)[2 * c] = f32x4{f[0], f[1], f[2], f[3]};
+        reinterpret_cast<f32x4*>(row)[2 * c + 1] = f32x4{f[4], f[5], f[6], f[7]};
+      } else {
+        row[c] = H::widen(q[k][0]);
+      }
+    }
+  };
+
+  const uint64_t stride = (uint64_t)gridDim.x * gpb;
+  uint64_t u = (uint64_t)blockIdx.x * gpb + (threadIdx.x >> lg);
+  uint32_t slot_next = u < m ? slots[u] : 0;
+  for (; u < m; u += stride) {
+    const uint32_t slot = slot_next;
+    if (u + stride < m) slot_next = slots[u + stride];  // the next row's slot, a row ahead
+    uint16_t* const rp = R + (uint64_t)slot * width;
+    // the row: issued here and used by the first step; a wide row that is summed
+    // first is issued behind the sum, in front of the blocks and the tree that hide it
+    constexpr bool kRowFirst = kAhead || MODE == kRowwiseEach;
+    uint32_t r[UPL][W];
+    if constexpr (kRowFirst) load_row(r, rp);
+    double acc = 0.0;
+    uint64_t key = 0;
+    if (l == 0) {
+      acc = A[slot];
+      if (hr.stochastic) key = hr.K[slot];
+    }
+    uint32_t p0, pe;
+    if constexpr (MODE == kRowwiseSame) {
+      p0 = 0, pe = (uint32_t)src.f.k;
+    } else {
+      p0 = src.seg ? src.seg[u] : (uint32_t)u;
+      pe = src.seg ? src.seg[u + 1] : p0 + 1;  // > p0: every unique key has an occurrence
+    }
+    // position p's gradient row index, the row itself and its factor
+    auto index = [&](uint32_t p) -> uint32_t {
+      if constexpr (MODE == kRowwiseSame) return p;
+      else return src.idx ? src.idx[p] : p;
+    };
+    auto where = [&](uint32_t ix) -> const float* {
+      if constexpr (MODE == kRowwiseSame) return (const float*)vals_at[ix] + u * width;
+      if (src.grads) return src.grads + (uint64_t)ix * width;
+      return (const float*)vals_at[frame_of(src.f, ix)] + (uint64_t)ix * width;
+    };
+    auto factor = [&](uint32_t p, uint32_t ix) -> float {
+      if (pool == kPoolWeighted) return src.w[p];
+      if (pool == kPoolMean) return (float)(uint32_t)(src.offsets[(uint64_t)ix + 1] - src.offsets[ix]);
+      return 0.0f;
+    };
+    // one step on r with the gradient s; acc and key are the group's in every lane
+    auto step = [&](const float (&s)[UPL][E]) __attribute__((always_inline)) {
+      // the words of this step, from A before it: a unit's block now, under the gradient loads
+      const uint64_t abits = __builtin_bit_cast(uint64_t, acc);
+      const uint32_t c2 = (uint32_t)abits ^ (uint32_t)(abits >> 32);
+      [[maybe_unused]] uint32_t words[VEC ? UPL : 1][4];
+      if constexpr (VEC) {
+        if (hr.stochastic) {
+#pragma unroll
+          for (int k = 0; k < UPL; ++k)
+            philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), c2, l + (uint32_t)k * G, hr.k0, hr.k1, words[k]);
+        }
+      }
+      auto sq = [&](int k, double y[E]) {
+        const bool in = l + (uint32_t)k * G < upr;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const double g = (double)(a.lr * s[k][e]);
+          y[e] = in ? g * g : 0.0;
+        }
+      };
+      double y[E];
+      sq_tree<1, 0, UPL, E>(sq, y);
+#pragma unroll
+      for (uint32_t d = 32; d >= 1; d >>= 1) {
+        if (d >= G) continue;
+#pragma unroll
+        for (int e = 0; e < E; ++e) y[e] = y[e] + __shfl_xor(y[e], (int)d, 64);
+      }
+      acc = acc + unit_tree<1, 0, E>(y) / a.width;
+      const double st = a.alr / (sqrt(acc) + a.eps);
+      // written out unit by unit, every index a constant (each_unit, as k_rows_pool_wgrad)
+      each_unit<0, UPL>([&](int k) __attribute__((always_inline)) {
+        [[maybe_unused]] uint32_t one[4];
+        if constexpr (!VEC) {
+          if (hr.stochastic) {
+            uint32_t kl = (uint32_t)key;
+            // the next element's rounds wait for this element's store word: 64 blocks are never alive at once
+            if constexpr (UPL > 16) {
+              if (k > 0) asm volatile("" : "+v"(kl) : "v"(r[k > 0 ? k - 1 : 0][0]));
+            }
+            philox4x32_10(kl, (uint32_t)(key >> 32), c2, (l + (uint32_t)k * G) >> 3, hr.k0, hr.k1, one);
+          }
+        }
+        uint32_t h[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          float se = s[k][e];
+          // wide rows: the product is made again here, not kept across the reduction
+          if constexpr (UPL * E > 16) asm volatile("" : "+v"(se));
+          const double g = (double)(a.lr * se);
+          const double d = st * g;
+          const float v = (float)((double)H::widen(half_of(r[k], e)) - d);
+          if (hr.stochastic) {
+            uint32_t w32;
+            if constexpr (VEC) {
+              w32 = words[k][e >> 1];
+            } else {
+              const uint32_t j = ((l + (uint32_t)k * G) >> 1) & 3u;
+              w32 = j == 0 ? one[0] : j == 1 ? one[1] : j == 2 ? one[2] : one[3];
+            }
+            const bool hi = VEC ? (e & 1) != 0 : ((l + (uint32_t)k * G) & 1u) != 0;
+            h[e] = H::stochastic(v, hi ? w32 >> 16 : w32 & 0xffffu);
+          } else {
+            h[e] = H::nearest(v);
+          }
+        }
+        if constexpr (VEC) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) r[k][j] = h[2 * j] | (h[2 * j + 1] << 16);
+        } else {
+          r[k][0] = h[0];
+        }
+      });
+    };
+
+    uint32_t i0 = index(p0);
+    uint32_t i1 = p0 + 1 < pe ? index(p0 + 1) : 0;
+    float v[UPL][E];
+    load(v, where(i0));
+    [[maybe_unused]] float f = 0.0f;
+    if constexpr (MODE == kRowwiseSum) f = factor(p0, i0);
+    acc = __shfl(acc, (int)head, 64);
+    key = __shfl(key, (int)head, 64);
+    [[maybe_unused]] float s[UPL][E] = {};  // +0.0f: the merge buffer starts from zero
+    for (uint32_t p = p0; p < pe; ++p) {
+      const uint32_t i2 = p + 2 < pe ? index(p + 2) : 0;
+      [[maybe_unused]] float vn[UPL][E];
+      [[maybe_unused]] float fn = 0.0f;
+      if constexpr (kAhead) {
+        if (p + 1 < pe) {
+          load(vn, where(i1));
+          if constexpr (MODE == kRowwiseSum) fn = factor(p + 1, i1);
+        }
+      }
+      if constexpr (MODE == kRowwiseEach) {
+        step(v);
+        if constexpr (PULL) store_reply(r, src.out + (uint64_t)i0 * width);
+      } else {
+#pragma unroll
+        for (int k = 0; k < UPL; ++k)
+#pragma unroll
+          for (int e = 0; e < E; ++e) {
+            float t = v[k][e];
+            if constexpr (MODE == kRowwiseSum) {
+              if (pool == kPoolWeighted) t = f * t;
+              else if (pool == kPoolMean) t = t / f;
+            }
+            s[k][e] = s[k][e] + t;
+          }
+      }
+      if (p + 1 < pe) {
+        if constexpr (kAhead) {
+#pragma unroll
+          for (int k = 0; k < UPL; ++k)
+#pragma unroll
+            for (int e = 0; e < E; ++e) v[k][e] = vn[k][e];
+          f = fn;
+        } else {
+          load(v, where(i1));
+          if constexpr (MODE == kRowwiseSum) f = factor(p + 1, i1);
+        }
+      }
+      i0 = i1, i1 = i2;
+    }
+    if constexpr (!kRowFirst) load_row(r, rp);
+    if constexpr (MODE != kRowwiseEach) step(s);
+    store_row(r, rp);
+    if (l == 0) A[slot] = acc;
+    if constexpr (PULL && MODE == kRowwiseSame) {
+      for (int j = 0; j < src.f.k; ++j) store_reply(r, (float*)out_at[j] + u * width);
+    }
+    if constexpr (PULL && MODE == kRowwiseSum) {
+      uint32_t j0 = index(p0);
+      for (uint32_t p = p0; p < pe; ++p) {
+        const uint32_t jn = p + 1 < pe ? index(p + 1) : 0;
+        store_reply(r, (float*)out_at[frame_of(src.f, j0)] + (uint64_t)j0 * width);
+        j0 = jn;
+      }
+    }
+  }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 // A[to[j]] (to null: A[j]) = value for j < n: the accumulators of new rows
 __global__ __launch_bounds__(256) void k_accum_fill(double* __restrict__ A, const uint32_t* __restrict__ to, uint64_t n,
                                                     double value) {
@@ -1986,6 +2344,12 @@ int require_iteration(const char* name, int iteration) {
 int require_f32(const char* name, const psg_table* t) {
   PSG_REQUIRE(t->dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: the update is built for F32 tables", name);
   return PSG_OK;
+}
+bool is_half(const psg_table* t) { return t->dtype == PSG_F16 || t->dtype == PSG_BF16; }
+// what an update call takes: F32, or 16-bit rows with psg_table_set_adagrad_half's state
+int require_trainable(const char* name, const psg_table* t) {
+  if (is_half(t) && t->adagrad) return PSG_OK;
+  return require_f32(name, t);
 }
 
 // ---- rows as raw bytes ------------------------------------------------------------
@@ -2466,9 +2830,49 @@ int launch_rowwise(psg_table* t, bool vec, const RowwiseSrc& src, uint64_t m, fl
   PSG_HIP(hipGetLastError());
   return PSG_OK;
 }
+// k_rows_walk_rowwise_half over m unique rows of an F16 / BF16 table.  vec is the
+// caller's (every gradient and reply array on 16 B); a 16-B unit of the row is eight
+// columns, so the width must divide by 8, too.  G and UPL as above: 1, 4 or 8 units
+// of eight columns cover 4096; element units 1, 4, 16, 64.
+template <int DT, int MODE, bool PULL>
+int launch_rowwise_half(psg_table* t, bool vec, const RowwiseSrc& src, uint64_t m, float lr, hipStream_t st) {
+  vec = vec && t->width % 8 == 0;
+  const uint32_t upr = vec ? t->width / 8 : t->width;
+  uint32_t lg = 0;
+  while (lg < 6 && (1u << lg) < upr) ++lg;
+  const uint32_t need = (upr + 63) / 64;
+  const uint32_t gpb = (uint32_t)kBlock >> lg;
+  const unsigned grid = grid_for((m + gpb - 1) / gpb);
+  const RowwiseArgs a = {lr, t->ag_lr, t->ag_eps, (double)t->width};
+  const HalfRound hr = {t->keys, (uint32_t)t->ag_seed, (uint32_t)(t->ag_seed >> 32), t->ag_round == PSG_ROUND_STOCHASTIC};
+  auto go = [&](auto v, auto upl) {
+    k_rows_walk_rowwise_half<DT, decltype(v)::value, decltype(upl)::value, MODE, PULL>
+        <<<grid, kBlock, 0, st>>>((uint16_t*)t->rows, t->accum, t->slots, src, m, upr, lg, a, hr);
+  };
+  using std::integral_constant;
+  if (vec) {
+    if (need <= 1) go(std::true_type{}, integral_constant<int, 1>{});
+    else if (need <= 4) go(std::true_type{}, integral_constant<int, 4>{});
+    else go(std::true_type{}, integral_constant<int, 8>{});
+  } else {
+    if (need <= 1) go(std::false_type{}, integral_constant<int, 1>{});
+    else if (need <= 4) go(std::false_type{}, integral_constant<int, 4>{});
+    else if (need <= 16) go(std::false_type{}, integral_constant<int, 16>{});
+    else go(std::false_type{}, integral_constant<int, 64>{});
+  }
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+// the Adagrad step of an update call, by the table's dtype
+template <int MODE, bool PULL>
+int launch_adagrad(psg_table* t, bool vec, const RowwiseSrc& src, uint64_t m, float lr, hipStream_t st) {
+  if (t->dtype == PSG_F16) return launch_rowwise_half<PSG_F16, MODE, PULL>(t, vec, src, m, lr, st);
+  if (t->dtype == PSG_BF16) return launch_rowwise_half<PSG_BF16, MODE, PULL>(t, vec, src, m, lr, st);
+  return launch_rowwise<MODE, PULL>(t, vec, src, m, lr, st);
+}
 template <int MODE>
-int launch_rowwise(psg_table* t, bool pull, bool vec, const RowwiseSrc& src, uint64_t m, float lr, hipStream_t st) {
-  return pull ? launch_rowwise<MODE, true>(t, vec, src, m, lr, st) : launch_rowwise<MODE, false>(t, vec, src, m, lr, st);
+int launch_adagrad(psg_table* t, bool pull, bool vec, const RowwiseSrc& src, uint64_t m, float lr, hipStream_t st) {
+  return pull ? launch_adagrad<MODE, true>(t, vec, src, m, lr, st) : launch_adagrad<MODE, false>(t, vec, src, m, lr, st);
 }
 
 // The body of the four request calls; `name` is the call's, for its messages.
@@ -2480,7 +2884,7 @@ int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const u
   if (opt) {
     PSG_TRY(require_update_flags(name, flags));
     PSG_TRY(require_iteration(name, iteration));
-    PSG_TRY(require_f32(name, t));
+    PSG_TRY(require_trainable(name, t));
   } else {
     PSG_REQUIRE(flags >= 1 && flags <= 3, PSG_ERR_INVALID, "%s: bad flags %d", name, flags);
   }
@@ -2513,7 +2917,7 @@ int serve(const char* name, bool opt, bool any, psg_table* t, int flags, const u
       src.idx = p ? p->perm : nullptr;
       src.grads = (const float*)vals;
       src.out = (float*)out;
-      PSG_TRY(launch_rowwise<kRowwiseEach>(t, (flags & PSG_PULL) != 0, vec, src, p ? p->m : n, lr, st));
+      PSG_TRY(launch_adagrad<kRowwiseEach>(t, (flags & PSG_PULL) != 0, vec, src, p ? p->m : n, lr, st));
     } else
     PSG_TRY(with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
       return launch_op<typename decltype(unit)::type>(t, flags, p, vals, out, n, upr, prm, st);
@@ -2824,7 +3228,7 @@ int pooled_step(psg_table* t, bool vec, const AnyPlan* p, const uint32_t* bags, 
     src.w = sc.weights;
     src.offsets = sc.weights ? nullptr : sc.offsets;
     if (f) src.f = *f;
-    return launch_rowwise<kRowwiseSum, false>(t, vec, src, p ? p->m : n, lr, st);
+    return launch_adagrad<kRowwiseSum, false>(t, vec, src, p ? p->m : n, lr, st);
   }
   return with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
     return launch_walk_pool<typename decltype(unit)::type>(t, p, bags, grads, f, sc, n, upr, prm, st);
@@ -2858,7 +3262,7 @@ int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
   PSG_TRY(require_iteration(name, iteration));
   PSG_TRY(require_count(name, n));
   PSG_TRY(require_count(name, nb, "bags"));
-  PSG_TRY(require_f32(name, t));
+  PSG_TRY(require_trainable(name, t));
   if (nb == 0) return PSG_OK;
   hipStream_t st = (hipStream_t)stream;
   // the offsets check in front of the resolve: both raise their flags in
@@ -2909,6 +3313,43 @@ int update_pooled(const char* name, psg_table* t, const uint64_t* keys, const ui
   // complete on return: keys, offsets, weights and grads no longer read
   PSG_HIP(hipStreamSynchronize(st));
   if (path) *path = strict ? PSG_MERGED_SAME_LIST : PSG_MERGED_SORTED;
+  return PSG_OK;
+}
+
+// ---- what the two Adagrad setters share --------------------------------------------
+// the four refusals behind the dtype's, in the header's order
+int adagrad_args(const char* name, const psg_table* t, double learning_rate, double epsilon,
+                 double initial_accumulator) {
+  PSG_REQUIRE(!t->adam && !t->adagrad, PSG_ERR_INVALID, "%s: the table already has %s state", name,
+              t->adam ? "Adam" : "Adagrad");
+  PSG_REQUIRE(std::isfinite(learning_rate), PSG_ERR_INVALID, "%s: learning_rate %g is not finite", name, learning_rate);
+  PSG_REQUIRE(std::isfinite(epsilon) && epsilon >= 0, PSG_ERR_INVALID, "%s: epsilon %g negative or not finite", name,
+              epsilon);
+  PSG_REQUIRE(std::isfinite(initial_accumulator) && initial_accumulator >= 0, PSG_ERR_INVALID,
+              "%s: initial_accumulator %g negative or not finite", name, initial_accumulator);
+  return PSG_OK;
+}
+// A[capacity], initial_accumulator for every row present, and the three parameters
+int adagrad_attach(const char* name, psg_table* t, double learning_rate, double epsilon, double initial_accumulator) {
+  t->ag_init = initial_accumulator;
+  if (t->capacity) {
+    double* accum = nullptr;
+    PSG_HIP(hipMalloc((void**)&accum, t->capacity * sizeof(double)));
+    // on the null stream, waited for: done before the caller's streams use the accumulators
+    int rc = t->size ? fill_accum(t, accum, nullptr, t->size, nullptr) : (int)PSG_OK;
+    if (rc == PSG_OK) {
+      const hipError_t e = hipStreamSynchronize(nullptr);
+      if (e != hipSuccess) rc = hip_fail(e, name, __FILE__, __LINE__);
+    }
+    if (rc != PSG_OK) {
+      (void)hipFree(accum);
+      return rc;
+    }
+    t->accum = accum;
+  }
+  t->adagrad = 1;
+  t->ag_lr = learning_rate;
+  t->ag_eps = epsilon;
   return PSG_OK;
 }
 
@@ -3041,32 +3482,28 @@ int psg_table_set_adagrad(psg_table* t, double learning_rate, double epsilon, do
   const char* name = "psg_table_set_adagrad";
   PSG_TRY(require_table(name, t));
   PSG_TRY(require_f32(name, t));
-  PSG_REQUIRE(!t->adam && !t->adagrad, PSG_ERR_INVALID, "%s: the table already has %s state", name,
-              t->adam ? "Adam" : "Adagrad");
-  PSG_REQUIRE(std::isfinite(learning_rate), PSG_ERR_INVALID, "%s: learning_rate %g is not finite", name, learning_rate);
-  PSG_REQUIRE(std::isfinite(epsilon) && epsilon >= 0, PSG_ERR_INVALID, "%s: epsilon %g negative or not finite", name,
-              epsilon);
-  PSG_REQUIRE(std::isfinite(initial_accumulator) && initial_accumulator >= 0, PSG_ERR_INVALID,
-              "%s: initial_accumulator %g negative or not finite", name, initial_accumulator);
-  t->ag_init = initial_accumulator;
-  if (t->capacity) {
-    double* accum = nullptr;
-    PSG_HIP(hipMalloc((void**)&accum, t->capacity * sizeof(double)));
-    // on the null stream, waited for: done before the caller's streams use the accumulators
-    int rc = t->size ? fill_accum(t, accum, nullptr, t->size, nullptr) : (int)PSG_OK;
-    if (rc == PSG_OK) {
-      const hipError_t e = hipStreamSynchronize(nullptr);
-      if (e != hipSuccess) rc = hip_fail(e, name, __FILE__, __LINE__);
-    }
-    if (rc != PSG_OK) {
-      (void)hipFree(accum);
-      return rc;
-    }
-    t->accum = accum;
-  }
-  t->adagrad = 1;
-  t->ag_lr = learning_rate;
-  t->ag_eps = epsilon;
+  PSG_TRY(adagrad_args(name, t, learning_rate, epsilon, initial_accumulator));
+  return adagrad_attach(name, t, learning_rate, epsilon, initial_accumulator);
+}
+
+int psg_table_set_adagrad_half(psg_table* t, double learning_rate, double epsilon, double initial_accumulator,
+                               int rounding, uint64_t seed) {
+  const char* name = "psg_table_set_adagrad_half";
+  PSG_TRY(require_table(name, t));
+  PSG_REQUIRE(is_half(t), PSG_ERR_UNSUPPORTED, "%s: the table is neither F16 nor BF16", name);
+  PSG_TRY(adagrad_args(name, t, learning_rate, epsilon, initial_accumulator));
+  PSG_REQUIRE(rounding == PSG_ROUND_NEAREST || rounding == PSG_ROUND_STOCHASTIC, PSG_ERR_INVALID,
+              "%s: rounding %d is no rounding mode", name, rounding);
+  PSG_TRY(adagrad_attach(name, t, learning_rate, epsilon, initial_accumulator));
+  t->ag_round = rounding;
+  t->ag_seed = seed;
+  return PSG_OK;
+}
+
+int psg_table_get_rounding(psg_table* t, int* rounding, uint64_t* seed) {
+  PSG_REQUIRE(t && rounding && seed, PSG_ERR_INVALID, "psg_table_get_rounding: null argument");
+  *rounding = t->ag_round;
+  *seed = t->ag_seed;
   return PSG_OK;
 }
 
@@ -3125,7 +3562,7 @@ int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* cons
     f.out[j] = pull ? outs[j] : nullptr;
     vec = vec && aligned16(grads[j]) && (!pull || aligned16(outs[j]));  // optimize_vec's condition, every frame
   }
-  PSG_TRY(require_f32(name, t));
+  PSG_TRY(require_trainable(name, t));
   if (path_host) *path_host = 0;
   if (N == 0) return PSG_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -3174,9 +3611,9 @@ int psg_table_update_merged(psg_table* t, int flags, int k, const uint64_t* cons
     src.f = f;
     if (p) {  // grads stays null: a position of the concatenation picks its frame
       src.seg = p->seg, src.idx = p->perm;
-      PSG_TRY(launch_rowwise<kRowwiseSum>(t, pull, vec, src, p->m, lr, st));
+      PSG_TRY(launch_adagrad<kRowwiseSum>(t, pull, vec, src, p->m, lr, st));
     } else {
-      PSG_TRY(launch_rowwise<kRowwiseSame>(t, pull, vec, src, n, lr, st));
+      PSG_TRY(launch_adagrad<kRowwiseSame>(t, pull, vec, src, n, lr, st));
     }
   } else
   PSG_TRY(with_opt_unit(t, vec, lr, iteration, [&](auto unit, uint32_t upr, const auto& prm) {
@@ -3444,7 +3881,7 @@ int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* k
     N += ns[j];
     G += g;
   }
-  PSG_TRY(require_f32(name, t));
+  PSG_TRY(require_trainable(name, t));
   if (path_host) *path_host = 0;
   if (!pooled) return psg_table_update_merged(t, PSG_PUSH, k, keys, ns, grads, nullptr, lr, iteration, stream, path_host);
   if (k == 1)

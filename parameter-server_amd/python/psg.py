@@ -29,6 +29,7 @@ PUSH, PULL = 1, 2
 RUN_ONE_BY_ONE, RUN_SAME_LIST, RUN_STRIDED = 0, 1, 2
 MERGED_SAME_LIST, MERGED_SORTED = 1, 2
 POOL_SUM, POOL_MEAN = 0, 1
+ROUND_NEAREST, ROUND_STOCHASTIC = 0, 1  # PSG_ROUND_*: how psg_table_set_adagrad_half's step rounds
 INIT_ZERO, INIT_UNIFORM = 0, 1
 H2D, D2H, D2D = 0, 1, 2
 
@@ -59,6 +60,7 @@ EXPORTS = [
     "psg_table_pooled_weight_grad",
     "psg_table_set_init", "psg_table_get_init", "psg_init_rows",
     "psg_table_set_adagrad", "psg_table_get_adagrad", "psg_table_dump_accum",
+    "psg_table_set_adagrad_half", "psg_table_get_rounding",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
     "psg_pool_reduce_mean", "psg_pool_scale_mean",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
@@ -174,6 +176,8 @@ def lib() -> C.CDLL:
             "psg_table_set_adagrad": ([vp, f64, f64, f64], i32),
             "psg_table_get_adagrad": ([vp, C.POINTER(i32), C.POINTER(f64)], i32),
             "psg_table_dump_accum": ([vp, vp], i32),
+            "psg_table_set_adagrad_half": ([vp, f64, f64, f64, i32, u64], i32),
+            "psg_table_get_rounding": ([vp, C.POINTER(i32), C.POINTER(u64)], i32),
             "psg_table_assign": ([vp, vp, vp, vp, vp, u64, vp], i32),
             "psg_table_export": ([vp, u64, u64, vp, vp, vp, vp, vp], i32),
             "psg_table_lookup": ([vp, vp, vp, vp, u64, vp], i32),
@@ -647,6 +651,19 @@ class Table:
         initial_accumulator for every row present and inserted later; every update
         call then takes its step in place of the SGD step."""
         _call("psg_table_set_adagrad", self.h, lr, eps, initial_accumulator)
+
+    def set_adagrad_half(self, lr: float, eps: float = 1e-8, initial_accumulator: float = 0.0,
+                         rounding: int = ROUND_STOCHASTIC, seed: int = 0) -> None:
+        """Row-wise Adagrad on an F16 / BF16 table (psg_table_set_adagrad_half): the
+        state of set_adagrad, gradients and replies in f32, and the stored half
+        rounded to nearest or stochastically by counter-based words under `seed`."""
+        _call("psg_table_set_adagrad_half", self.h, lr, eps, initial_accumulator, rounding, seed)
+
+    def rounding(self):
+        """(rounding mode, seed) as set_adagrad_half got them; zeros without it."""
+        mode, seed = C.c_int(0), C.c_uint64(0)
+        _call("psg_table_get_rounding", self.h, C.byref(mode), C.byref(seed))
+        return mode.value, seed.value
 
     def adagrad(self):
         """None, or the (lr, eps, initial_accumulator) set_adagrad got."""
