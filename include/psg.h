@@ -34,6 +34,9 @@
  *                    the weighted bag's gradient with respect to its weights
  *   psg_table_update_pooled_merged
  *                    the sync-mode round over k frames, pooled or plain
+ *   psg_table_freeze_q8 / psg_qtable_*
+ *                    a frozen 8-bit row-wise copy of a table, looked up and
+ *                    pooled (no such object in the reference)
  *   psg_server_ranges PostOffice::GetServerRanges        src/internal/PostOffice.cpp:211-221
  *   psg_slice        KVWorker<V>::DefaultSlicer           src/ps/KVApp.h:515-574
  *   psg_merge        the AddPullCB merge lambda           src/ps/KVApp.h:673-726
@@ -1050,6 +1053,112 @@ int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* k
                                    const uint64_t* ns_host, const uint64_t* const* offsets_host,
                                    const uint64_t* nbs_host, const float* const* grads_host,
                                    float lr, int iteration, psg_stream stream, int* path_host);
+
+/* ======================================================================== */
+/* Frozen 8-bit row-wise snapshot of a row table                              */
+/* ======================================================================== */
+/* A psg_qtable is an immutable copy of a table's keys and rows for serving:
+ * `size` strictly ascending uint64 keys in [key_begin, key_end), and per key one
+ * row of `width` (1 .. 4096) uint8 codes with an f32 scale and an f32 bias of its
+ * own — the fused 8-bit row-wise layout of embedding libraries.  It is never
+ * inserted into, updated or erased from; the reference has nothing like it.
+ * Calls on one snapshot are serialised by the caller (it owns request scratch).
+ *
+ * THE FROZEN ROW.  All arithmetic is f32, every operation is rounded once and
+ * nothing is fused (the library is built with -ffp-contract=off).  x[j] is the
+ * source row's column j widened to f32 (exact for F16 and BF16):
+ *   lo    = min_j x[j],  hi = max_j x[j]   -- exact; -0.0 ranks below +0.0, so the
+ *                                             order of the reduction changes no bit
+ *   bias  = lo + 0.0f                      -- a -0.0 minimum is stored as +0.0
+ *   range = hi - lo
+ *   scale = range / 255.0f                 -- a correctly rounded division
+ *   code[j] = 0                                          where scale == 0
+ *           = min(rint((x[j] - lo) / scale), 255)        otherwise
+ * scale == 0 covers a constant row and a range so small that range / 255
+ * underflows.  The division is correctly rounded (no reciprocal), rint rounds to
+ * the nearest even integer, and the clamp is needed: the quotient can reach
+ * 255.00002.  A code is read back as
+ *   xhat[j] = (float)code[j] * scale + bias              -- one multiply, then one add
+ * which is never -0.0: the sign of a -0.0 column is not kept.
+ * A source row that holds a NaN or an infinity, or whose range is not finite
+ * (-3e38 and 3e38 in one row), is refused.
+ *
+ * THE EXTERNAL FORMAT (psg_qtable_export writes it, psg_qtable_create reads it):
+ * row i is the width + 8 bytes at rows + i * (width + 8), no padding and no
+ * alignment: `width` codes, then scale, then bias, each a little-endian f32. */
+typedef struct psg_qtable psg_qtable;
+typedef struct psg_qtable_info {
+  uint32_t width;        /* codes per row */
+  uint32_t row_bytes;    /* width + 8: a row in the external format */
+  uint64_t size;         /* keys (rows) held */
+  uint64_t key_begin;    /* key range [key_begin, key_end) */
+  uint64_t key_end;
+  uint64_t device_bytes; /* device memory held now: keys, rows as stored, request scratch */
+} psg_qtable_info;
+
+/* Freeze table t into a new snapshot *out: its keys, its key range, and every row
+ * as THE FROZEN ROW defines it.  F32, F16 and BF16 tables.  t is read and not
+ * changed; its optimizer state and its initializer are not carried over (an id the
+ * snapshot does not hold reads as a +0.0 row).  An empty table gives a snapshot of
+ * size 0.  Refused before any device call, in this order: a null table, null out
+ * -> PSG_ERR_INVALID; an F64 table -> PSG_ERR_UNSUPPORTED.  A row the definition
+ * refuses fails the call with PSG_ERR_INVALID: nothing is made and *out is not
+ * written.  One kernel reads the source once; ONE host synchronisation, for that
+ * flag.  Returns with the snapshot complete and t no longer read. */
+int psg_table_freeze_q8(psg_table* t, psg_qtable** out, psg_stream stream);
+/* A snapshot from n rows in THE EXTERNAL FORMAT: keys (n device uint64, strictly
+ * ascending, inside [key_begin, key_end)) and rows (n * (width + 8) device bytes,
+ * any alignment).  Codes, scale and bias are taken as bytes and never re-derived.
+ * Refused with PSG_ERR_INVALID before any device call, in this order: null out;
+ * width outside [1, 4096]; an empty key range; null keys, then null rows, with n >
+ * 0; then with PSG_ERR_RANGE n above 2^32 - 2.  The keys are checked on the device
+ * with ONE synchronisation: not strictly ascending -> PSG_ERR_INVALID, a key
+ * outside the range -> PSG_ERR_RANGE, both -> PSG_ERR_INVALID; nothing is made and
+ * *out is not written.  Returns with keys and rows no longer read. */
+int psg_qtable_create(uint32_t width, uint64_t key_begin, uint64_t key_end, const uint64_t* keys,
+                      const void* rows, uint64_t n, psg_qtable** out, psg_stream stream);
+/* Frees the snapshot and its scratch.  NULL is a no-op. */
+int psg_qtable_destroy(psg_qtable* q);
+/* The snapshot as it is now.  Host only. */
+int psg_qtable_get_info(psg_qtable* q, psg_qtable_info* info);
+/* Rows [first, first + count) in key (slot) order into DEVICE arrays: keys_out
+ * (may be NULL) count keys, rows_out count * (width + 8) bytes in THE EXTERNAL
+ * FORMAT.  first + count above the size fails with PSG_ERR_INVALID.  Ordered on
+ * `stream` as psg_table_export is: the caller synchronises before it reads.
+ * count == 0 is a no-op. */
+int psg_qtable_export(psg_qtable* q, uint64_t first, uint64_t count, uint64_t* keys_out,
+                      void* rows_out, psg_stream stream);
+/* psg_table_lookup on a snapshot: n device keys in any order and with repeats;
+ * out (n * width device f32, or NULL) gets xhat of every key held and a +0.0 row
+ * for every other; found (n device bytes, or NULL) gets 1 / 0.  Refused with
+ * PSG_ERR_INVALID before any device call, in this order: a null snapshot; null
+ * keys; out and found both NULL; out not on a 4-B boundary (each with n > 0); then
+ * PSG_ERR_RANGE: n above 2^32 - 2.  A key outside [key_begin, key_end) fails the
+ * call with PSG_ERR_RANGE and neither out nor found is written.  Two kernels (the
+ * row table's any-order resolve, the read behind its flag on the device) and ONE
+ * host synchronisation, at the end.  n == 0 is a no-op. */
+int psg_qtable_lookup(psg_qtable* q, const uint64_t* keys, float* out, uint8_t* found, uint64_t n,
+                      psg_stream stream);
+/* The three poolings of psg_table_lookup_pooled / _lookup_pooled_weighted on a
+ * snapshot, into f32: keys, offsets, weights, mode, n and nb are theirs, out holds
+ * nb * width device f32.  The result is, bit for bit, what those calls give on an
+ * F32 table without initializer that holds the xhat rows: per bag and column the sum starts from
+ * +0.0 and runs in arrival order, acc = acc + xhat, or with weights acc = acc +
+ * (weights[p] * xhat), the product rounded before the add; PSG_POOL_MEAN divides
+ * the sum once by the bag's whole length, ids not held counted; an id not held
+ * adds nothing whatever its weight; an empty bag gives a +0.0 row.
+ * Refused before any device call, in this order, with PSG_ERR_INVALID: a null
+ * snapshot; null keys with n > 0; null offsets or null out with nb > 0; nb == 0
+ * with n > 0; mode outside {PSG_POOL_SUM, PSG_POOL_MEAN}; PSG_POOL_MEAN with
+ * weights; weights, then out, not on a 4-B boundary.  Then PSG_ERR_RANGE: n or nb
+ * above 2^32 - 2.  nb == 0 is a no-op.  Found on the device, and then out is not
+ * written: bad offsets -> PSG_ERR_INVALID, a key out of range -> PSG_ERR_RANGE,
+ * both -> PSG_ERR_INVALID; nothing is walked.  Three kernels (the row table's
+ * offsets check and resolve, the pooling behind their flags) and ONE host
+ * synchronisation, at the end. */
+int psg_qtable_lookup_pooled(psg_qtable* q, const uint64_t* keys, const uint64_t* offsets,
+                             const float* weights, int mode, float* out, uint64_t n, uint64_t nb,
+                             psg_stream stream);
 
 /* ======================================================================== */
 /* Worker side: key-range slicing and pull merge                              */

@@ -366,6 +366,26 @@ struct EmitKey {  // dst = the hit keys
 };
 #endif
 
+// ---- the row table's front half, for psg_qrows.hip -----------------------------
+// What a frozen snapshot (psg_qtable) shares with the table it was made from: the
+// any-order resolve and the offsets check of psg_rows.hip, which take K, S and the
+// key range and not a table, behind launch functions; the flag words both raise
+// (psg_rows.hip's R_RANGE / R_OFFSETS of its kNFlags, asserted equal there) and the
+// slot of an absent key; and a table as the freeze reads it.
+constexpr int kRowFlagRange = 1, kRowFlagOffsets = 4, kRowFlags = 5;
+constexpr uint32_t kRowAbsent = 0xffffffffu;
+int rows_resolve_any(const uint64_t* q, uint64_t n, const uint64_t* K, uint64_t S, uint64_t kb, uint64_t ke,
+                     uint32_t* slots, int* flags, hipStream_t st);
+int rows_offsets_check(const uint64_t* offsets, uint64_t n, uint64_t nb, int* flags, hipStream_t st);
+struct TableView {
+  int dtype;
+  uint32_t width;
+  uint64_t key_begin, key_end, size;
+  const uint64_t* keys;
+  const void* rows;
+};
+TableView table_view(const psg_table* t);  // host fields only: no device call
+
 // Bytes to hipMalloc for an array a peer process may map (hipIpc): the HIP
 // runtime may carve allocations below 2 MiB out of a shared block, and such a
 // pointer's IPC handle cannot always be opened ("invalid device pointer"), so

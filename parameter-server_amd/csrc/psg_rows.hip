@@ -3354,6 +3354,22 @@ int adagrad_attach(const char* name, psg_table* t, double learning_rate, double 
 }
 
 }  // namespace
+
+// ---- what a frozen snapshot (psg_qrows.hip) takes from this file ---------------------
+static_assert(kRowFlagRange == R_RANGE && kRowFlagOffsets == R_OFFSETS && kRowFlags == kNFlags &&
+              kRowAbsent == kAbsent, "psg_internal.h names this file's flag words and absent slot");
+int rows_resolve_any(const uint64_t* q, uint64_t n, const uint64_t* K, uint64_t S, uint64_t kb, uint64_t ke,
+                     uint32_t* slots, int* flags, hipStream_t st) {
+  k_rows_resolve_any<<<grid_for((n + kRowTile - 1) / kRowTile), kBlock, 0, st>>>(q, n, K, S, kb, ke, slots, flags);
+  PSG_HIP(hipGetLastError());
+  return PSG_OK;
+}
+int rows_offsets_check(const uint64_t* offsets, uint64_t n, uint64_t nb, int* flags, hipStream_t st) {
+  return launch_offsets_check(offsets, n, nb, flags, st);
+}
+TableView table_view(const psg_table* t) {
+  return {t->dtype, t->width, t->key_begin, t->key_end, t->size, t->keys, t->rows};
+}
 }  // namespace psg
 
 using namespace psg;

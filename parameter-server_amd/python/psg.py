@@ -61,6 +61,8 @@ EXPORTS = [
     "psg_table_set_init", "psg_table_get_init", "psg_init_rows",
     "psg_table_set_adagrad", "psg_table_get_adagrad", "psg_table_dump_accum",
     "psg_table_set_adagrad_half", "psg_table_get_rounding",
+    "psg_table_freeze_q8", "psg_qtable_create", "psg_qtable_destroy", "psg_qtable_get_info", "psg_qtable_export",
+    "psg_qtable_lookup", "psg_qtable_lookup_pooled",
     "psg_route", "psg_rows_gather", "psg_rows_scatter", "psg_route_bags", "psg_pool_reduce",
     "psg_pool_reduce_mean", "psg_pool_scale_mean",
     "psg_server_ranges", "psg_slice", "psg_slice_hint", "psg_merge", "psg_comm_id_bytes", "psg_comm_get_id",
@@ -94,6 +96,11 @@ class TableInfo(C.Structure):
     _fields_ = [("dtype", C.c_int), ("width", C.c_uint32), ("key_begin", C.c_uint64),
                 ("key_end", C.c_uint64), ("size", C.c_uint64), ("capacity", C.c_uint64),
                 ("rows", C.c_void_p), ("keys", C.c_void_p)]
+
+
+class QTableInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("row_bytes", C.c_uint32), ("size", C.c_uint64),
+                ("key_begin", C.c_uint64), ("key_end", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
 class Segment(C.Structure):
@@ -191,6 +198,13 @@ def lib() -> C.CDLL:
             "psg_table_set_init": ([vp, i32, u64, f32, f32], i32),
             "psg_table_get_init": ([vp, C.POINTER(i32), C.POINTER(u64), C.POINTER(f32), C.POINTER(f32)], i32),
             "psg_init_rows": ([vp, vp, u64, i32, C.c_uint32, u64, f32, f32, vp], i32),
+            "psg_table_freeze_q8": ([vp, C.POINTER(vp), vp], i32),
+            "psg_qtable_create": ([C.c_uint32, u64, u64, vp, vp, u64, C.POINTER(vp), vp], i32),
+            "psg_qtable_destroy": ([vp], i32),
+            "psg_qtable_get_info": ([vp, C.POINTER(QTableInfo)], i32),
+            "psg_qtable_export": ([vp, u64, u64, vp, vp, vp], i32),
+            "psg_qtable_lookup": ([vp, vp, vp, vp, u64, vp], i32),
+            "psg_qtable_lookup_pooled": ([vp, vp, vp, vp, i32, vp, u64, u64, vp], i32),
             "psg_server_ranges": ([i32, vp, vp], i32),
             "psg_slice": ([vp, u64, vp, u64, i32, vp, vp, vp, vp, vp], i32),
             "psg_merge": ([C.POINTER(Segment), i32, i32, vp, u64, vp], i32),
@@ -755,9 +769,65 @@ class Table:
               (C.c_uint64 * k)(*nbs), arr(2), lr, iteration, _s(stream), C.byref(path))
         return path.value
 
+    def freeze_q8(self, stream=None) -> "QTable":
+        """A frozen 8-bit row-wise snapshot of the table as it is now
+        (psg_table_freeze_q8): F32 / F16 / BF16 tables; the table is unchanged."""
+        h = C.c_void_p(None)
+        _call("psg_table_freeze_q8", self.h, C.byref(h), _s(stream))
+        return QTable(h, self.width)
+
     def close(self) -> None:
         if self.h.value:
             _call("psg_table_destroy", self.h)
+            self.h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class QTable:
+    """A frozen 8-bit row-wise snapshot (psg_qtable_*): per key `width` uint8 codes
+    with an f32 scale and bias, read back as code * scale + bias.  Immutable."""
+
+    def __init__(self, h, width: int):
+        self.h = h
+        self.width = width
+
+    @classmethod
+    def from_rows(cls, width: int, key_begin: int, key_end: int, keys, rows, n: int, stream=None) -> "QTable":
+        """From n exported rows (psg_qtable_create): keys ascending, rows n * (width + 8)
+        device bytes, each `width` codes then scale and bias as little-endian f32."""
+        h = C.c_void_p(None)
+        _call("psg_qtable_create", width, key_begin, key_end, _ptr(keys), _ptr(rows), n, C.byref(h), _s(stream))
+        return cls(h, width)
+
+    def info(self) -> QTableInfo:
+        i = QTableInfo()
+        _call("psg_qtable_get_info", self.h, C.byref(i))
+        return i
+
+    def export(self, first: int, count: int, keys_out, rows_out, stream=None) -> None:
+        """Rows [first, first + count) into device arrays in the external format
+        (psg_qtable_export); stream-ordered: synchronise before reading."""
+        _call("psg_qtable_export", self.h, first, count, _ptr(keys_out), _ptr(rows_out), _s(stream))
+
+    def lookup(self, keys, out, found, n: int, stream=None) -> None:
+        """Table.lookup on the snapshot (psg_qtable_lookup): out gets n * width float32,
+        a +0.0 row for an id not held; found n bytes.  Either may be None."""
+        _call("psg_qtable_lookup", self.h, _ptr(keys), _ptr(out), _ptr(found), n, _s(stream))
+
+    def lookup_pooled(self, keys, offsets, weights, mode: int, out, n: int, nb: int, stream=None) -> None:
+        """Table.lookup_pooled_weighted on the snapshot (psg_qtable_lookup_pooled): nb
+        float32 rows, bit for bit an F32 table's bags over the read-back rows."""
+        _call("psg_qtable_lookup_pooled", self.h, _ptr(keys), _ptr(offsets), _ptr(weights), mode, _ptr(out), n, nb,
+              _s(stream))
+
+    def close(self) -> None:
+        if self.h.value:
+            _call("psg_qtable_destroy", self.h)
             self.h = C.c_void_p(None)
 
     def __del__(self):
