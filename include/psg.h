@@ -34,6 +34,8 @@
  *                    the weighted bag's gradient with respect to its weights
  *   psg_table_update_pooled_merged
  *                    the sync-mode round over k frames, pooled or plain
+ *   psg_table_lookup_pooled_batch
+ *                    the pooled lookups of many tables in one call, two kernels
  *   psg_table_freeze_q8 / psg_qtable_*
  *                    a frozen 8-bit row-wise copy of a table, looked up and
  *                    pooled (no such object in the reference)
@@ -1053,6 +1055,56 @@ int psg_table_update_pooled_merged(psg_table* t, int k, const uint64_t* const* k
                                    const uint64_t* ns_host, const uint64_t* const* offsets_host,
                                    const uint64_t* nbs_host, const float* const* grads_host,
                                    float lr, int iteration, psg_stream stream, int* path_host);
+/* The pooled lookups of MANY tables in one call: a model's tables, each with its
+ * own bag list, side by side.  The eight *_host arguments are host arrays of T
+ * entries, 1 <= T <= PSG_BATCH_MAX (weights_host may be NULL as a whole: no entry
+ * has weights); keys_host, offsets_host, weights_host and outs_host hold DEVICE
+ * pointers.  Entry i is one request, and for every entry that is served outs[i]
+ * is, bit for bit, what
+ *   psg_table_lookup_pooled_weighted(tables[i], keys[i], offsets[i], weights[i],
+ *                                    modes[i], outs[i], ns[i], nbs[i], stream)
+ * gives on its own: that call's arrival order, accumulator type, one add per id
+ * (one multiply, then one add, with weights; never fused), one division for
+ * PSG_POOL_MEAN, halves rounded once, absent ids (nothing, or the initial row of
+ * a table with psg_table_set_init), empty bags (+0) and unit choice (16-B units
+ * where a row is a multiple of 16 B and outs[i] is on 16 B, else elements) are
+ * not restated here.  Nothing is ever inserted.
+ * What differs from T calls:
+ *   - The tables are only read: not their rows, keys or size, and not their
+ *     request scratch either.  The call keeps scratch of its own per thread and
+ *     GPU (descriptors, sum(ns) slot words, five gate words an entry, pinned
+ *     mirrors); a steady caller allocates nothing.  So one table may appear in
+ *     several entries, and the device pointers of psg_table_info stay as they were.
+ *   - Entries may differ in width (1 .. 4096), pooling mode, weights and
+ *     initializer; all tables of one call share ONE dtype, any of the four.
+ *   - The device work is fixed whatever T is: one H2D copy of the descriptors, one
+ *     clear of the gate words, TWO kernels (every entry's offsets check and
+ *     any-order resolve; every entry's pooling behind its entry's gate words) and
+ *     ONE host synchronisation, at the end.
+ *   - status_host (may be NULL) gets one code per entry: PSG_OK; PSG_ERR_INVALID,
+ *     the entry's offsets break one of psg_table_lookup_pooled's three rules;
+ *     PSG_ERR_RANGE, a key of the entry lies outside its table's range; both ->
+ *     PSG_ERR_INVALID.  A refused entry's out is not written and none of its
+ *     offsets are walked; every other entry is served (as psg_store_run_status
+ *     serves the rest of a run).  Returns PSG_OK when every entry was served, else
+ *     the status of the lowest-indexed refused entry.
+ *   - An entry with nbs[i] == 0 (and ns[i] == 0) is a no-op with status PSG_OK;
+ *     its pointers may be NULL.
+ * Refused as a whole before any device call, status_host not written, in this
+ * order: PSG_ERR_INVALID for T outside [1, PSG_BATCH_MAX]; any of tables_host,
+ * keys_host, offsets_host, modes_host, outs_host, ns_host, nbs_host null; then
+ * per entry in index order what the per-table call refuses: a null table; null
+ * keys with ns[i] > 0; null offsets or null out with nbs[i] > 0; nbs[i] == 0 with
+ * ns[i] > 0; a mode outside {PSG_POOL_SUM, PSG_POOL_MEAN}; PSG_POOL_MEAN with
+ * weights; weights not on a 4-B boundary.  Then PSG_ERR_RANGE: an ns[i] or nbs[i]
+ * above 2^32 - 2.  Then PSG_ERR_UNSUPPORTED: tables of more than one dtype.
+ * Complete on return, as psg_table_lookup_pooled is. */
+#define PSG_BATCH_MAX 1024
+int psg_table_lookup_pooled_batch(int T, psg_table* const* tables_host,
+                                  const uint64_t* const* keys_host, const uint64_t* const* offsets_host,
+                                  const float* const* weights_host, const int* modes_host,
+                                  void* const* outs_host, const uint64_t* ns_host,
+                                  const uint64_t* nbs_host, psg_stream stream, int* status_host);
 
 /* ======================================================================== */
 /* Frozen 8-bit row-wise snapshot of a row table                              */

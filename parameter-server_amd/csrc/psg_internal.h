@@ -174,6 +174,89 @@ template <int DT> struct PoolAcc<DT, false> {
   __device__ static __forceinline__ A over(A a, uint32_t len) { return a / (E)len; }
   __device__ static __forceinline__ U round(A a) { return (U)a; }
 };
+
+// ---- the initial rows (psg_table_set_init / psg_init_rows) ------------------------
+// Element j of the initial row of key K (include/psg.h): word j % 4 of
+// Philox4x32-10 on the counter {K lo, K hi, j / 4, 0} under the key {seed lo,
+// seed hi}; its upper 24 bits as u in [0, 1); lo + u * span in f32, the multiply
+// and the add each rounded (the library is built with -ffp-contract=off); then the
+// table's dtype.  Nothing else enters, so a row is the same wherever and
+// whenever it is made: in the insert's fill, in a lookup that finds its key
+// absent, on another server, after a restart.
+// A block is ten rounds of two 32 x 32 -> 64 multiplies (20 v_mad_u64_u32).
+struct InitSpec {
+  uint32_t k0, k1;  // the seed's words
+  float lo, span;   // span = hi - lo, subtracted once on the host
+};
+inline InitSpec init_spec(uint64_t seed, float lo, float hi) {
+  return {(uint32_t)seed, (uint32_t)(seed >> 32), lo, hi - lo};
+}
+
+__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                       uint32_t k1, uint32_t x[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c0 = n0, c1 = (uint32_t)p1, c2 = n2, c3 = (uint32_t)p0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
+}
+
+// block b of key's initial row: elements 4b .. 4b + 3 as f32
+__device__ __forceinline__ void init_block(uint64_t key, uint32_t b, const InitSpec& s, float v[4]) {
+  uint32_t x[4];
+  philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), b, 0u, s.k0, s.k1, x);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float u = (float)(x[e] >> 8) * 0x1p-24f;  // exact
+    const float prod = u * s.span;
+    v[e] = s.lo + prod;
+  }
+}
+
+// v[w] for a word index that is not a constant: selects, no indexed register file
+__device__ __forceinline__ float pick4(const float v[4], uint32_t w) {
+  return w == 0 ? v[0] : w == 1 ? v[1] : w == 2 ? v[2] : v[3];
+}
+
+// Unit c of key's initial row as the table stores it.  VEC: the 16-B unit (F32:
+// one block; F16 / BF16: blocks 2c and 2c + 1, rounded to nearest even; F64:
+// half of block c / 2, widened), else element c (its block, one word kept).
+template <int DT, bool VEC> struct InitUnit;
+template <int DT> struct InitUnit<DT, true> {
+  typedef u32x4 U;
+  __device__ static __forceinline__ U make(uint64_t key, uint32_t c, const InitSpec& s) {
+    float v[8];
+    if constexpr (DT == PSG_F32) {
+      init_block(key, c, s, v);
+      return __builtin_bit_cast(U, f32x4{v[0], v[1], v[2], v[3]});
+    } else if constexpr (DT == PSG_F64) {
+      init_block(key, c >> 1, s, v);
+      const bool up = (c & 1) != 0;
+      return __builtin_bit_cast(U, f64x2{(double)(up ? v[2] : v[0]), (double)(up ? v[3] : v[1])});
+    } else {
+      init_block(key, 2 * c, s, v);
+      init_block(key, 2 * c + 1, s, v + 4);
+      typename PoolVec<DT>::A a = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+      return __builtin_bit_cast(U, __builtin_convertvector(a, typename PoolVec<DT>::V));
+    }
+  }
+};
+template <int DT> struct InitUnit<DT, false> {
+  typedef typename Elem<DT>::T T;
+  typedef typename std::conditional<sizeof(T) == 8, uint64_t,
+                                    typename std::conditional<sizeof(T) == 4, uint32_t, uint16_t>::type>::type U;
+  __device__ static __forceinline__ U bits(float x) { return __builtin_bit_cast(U, (T)x); }
+  __device__ static __forceinline__ U make(uint64_t key, uint32_t c, const InitSpec& s) {
+    float v[4];
+    init_block(key, c >> 2, s, v);
+    return bits(pick4(v, c & 3));
+  }
+};
 #endif
 
 // ---- launch geometry --------------------------------------------------------
@@ -374,6 +457,7 @@ struct EmitKey {  // dst = the hit keys
 // slot of an absent key; and a table as the freeze reads it.
 constexpr int kRowFlagRange = 1, kRowFlagOffsets = 4, kRowFlags = 5;
 constexpr uint32_t kRowAbsent = 0xffffffffu;
+constexpr int kRowTile = 1024;  // request keys per block of the resolve (4 per lane)
 int rows_resolve_any(const uint64_t* q, uint64_t n, const uint64_t* K, uint64_t S, uint64_t kb, uint64_t ke,
                      uint32_t* slots, int* flags, hipStream_t st);
 int rows_offsets_check(const uint64_t* offsets, uint64_t n, uint64_t nb, int* flags, hipStream_t st);
@@ -383,6 +467,9 @@ struct TableView {
   uint64_t key_begin, key_end, size;
   const uint64_t* keys;
   const void* rows;
+  int init_kind;  // what an absent id reads as (psg_table_set_init): PSG_INIT_*, and its triple
+  uint64_t init_seed;
+  float init_lo, init_hi;
 };
 TableView table_view(const psg_table* t);  // host fields only: no device call
 

@@ -29,6 +29,7 @@ PUSH, PULL = 1, 2
 RUN_ONE_BY_ONE, RUN_SAME_LIST, RUN_STRIDED = 0, 1, 2
 MERGED_SAME_LIST, MERGED_SORTED = 1, 2
 POOL_SUM, POOL_MEAN = 0, 1
+BATCH_MAX = 1024  # PSG_BATCH_MAX: entries of one lookup_pooled_batch
 ROUND_NEAREST, ROUND_STOCHASTIC = 0, 1  # PSG_ROUND_*: how psg_table_set_adagrad_half's step rounds
 INIT_ZERO, INIT_UNIFORM = 0, 1
 H2D, D2H, D2D = 0, 1, 2
@@ -57,7 +58,7 @@ EXPORTS = [
     "psg_table_get_adam", "psg_table_assign", "psg_table_export",
     "psg_table_lookup", "psg_table_erase", "psg_table_lookup_pooled", "psg_table_update_pooled",
     "psg_table_lookup_pooled_weighted", "psg_table_update_pooled_weighted", "psg_table_update_pooled_merged",
-    "psg_table_pooled_weight_grad",
+    "psg_table_pooled_weight_grad", "psg_table_lookup_pooled_batch",
     "psg_table_set_init", "psg_table_get_init", "psg_init_rows",
     "psg_table_set_adagrad", "psg_table_get_adagrad", "psg_table_dump_accum",
     "psg_table_set_adagrad_half", "psg_table_get_rounding",
@@ -195,6 +196,7 @@ def lib() -> C.CDLL:
             "psg_table_update_pooled_weighted": ([vp, vp, vp, vp, i32, vp, u64, u64, f32, i32, vp], i32),
             "psg_table_pooled_weight_grad": ([vp, vp, vp, vp, vp, u64, u64, vp], i32),
             "psg_table_update_pooled_merged": ([vp, i32, vp, vp, vp, vp, vp, f32, i32, vp, C.POINTER(i32)], i32),
+            "psg_table_lookup_pooled_batch": ([i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)], i32),
             "psg_table_set_init": ([vp, i32, u64, f32, f32], i32),
             "psg_table_get_init": ([vp, C.POINTER(i32), C.POINTER(u64), C.POINTER(f32), C.POINTER(f32)], i32),
             "psg_init_rows": ([vp, vp, u64, i32, C.c_uint32, u64, f32, f32, vp], i32),
@@ -835,6 +837,26 @@ class QTable:
             self.close()
         except Exception:
             pass
+
+
+def lookup_pooled_batch(tables, keys, offsets, weights, modes, outs, ns, nbs, stream=None) -> list[int]:
+    """Table.lookup_pooled_weighted of many tables in one call, two kernels whatever
+    their number (psg_table_lookup_pooled_batch).  Lists of one entry per request:
+    its Table (one may serve several entries; one dtype a call), device keys,
+    offsets, weights or None (weights=None: no entry has any), mode, out, n and nb.
+    Returns the status per entry: 0, or the code of a refusal found on the device
+    (bad offsets, a key out of range), whose out is not written while every other
+    entry is served.  Raises PsgError only where the whole call was refused."""
+    T = len(tables)
+    ptrs = lambda xs: (C.c_void_p * T)(*[_ptr(x) for x in xs])
+    status = (C.c_int * T)(*([-1] * T))
+    rc = lib().psg_table_lookup_pooled_batch(
+        T, (C.c_void_p * T)(*[None if t is None else t.h.value for t in tables]), ptrs(keys), ptrs(offsets),
+        None if weights is None else ptrs(weights), (C.c_int * T)(*modes), ptrs(outs), (C.c_uint64 * T)(*ns),
+        (C.c_uint64 * T)(*nbs), _s(stream), status)
+    if rc != 0 and all(s == -1 for s in status):
+        check(rc, "psg_table_lookup_pooled_batch")
+    return list(status)
 
 
 def init_rows(out, keys, n: int, dtype: int, width: int, seed: int, lo: float, hi: float, stream=None) -> None:
